@@ -46,6 +46,55 @@ def test_bench_default_contract():
     assert d["config"]["global_batch"] == d["config"]["n_workers"]
 
 
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's aggregates as float32
+    .npy; the inputs are seeded, so a second run (here with --full, which
+    must not change the headline path) writes identical arrays."""
+    import numpy as np
+
+    dumps = []
+    for sub, extra in (("a", []), ("b", ["--full"])):
+        out = tmp_path / sub
+        r = _run(["bench.py", "--steps", "2", "--warmup", "1", "--d", "20000",
+                  "--dump-outputs", str(out)] + extra)
+        assert r.returncode == 0, r.stderr[-800:]
+        rec = json.loads(r.stdout.strip().splitlines()[-1])
+        assert rec["steps"] == 2 and rec["ms_per_step"] > 0
+        assert sorted(p.name for p in out.iterdir()) == [
+            "median.npy", "multi_krum.npy"]
+        dumps.append({p.name: np.load(p) for p in out.iterdir()})
+    for name, a in dumps[0].items():
+        assert a.dtype == np.float32 and a.shape == (20000,)
+        assert np.isfinite(a).all() and np.abs(a).max() > 0
+        assert np.array_equal(a, dumps[1][name]), name
+
+
+def test_bench_dump_outputs_samples_large_output(tmp_path):
+    """An output above the dump budget is written as a fixed-size sample."""
+    import numpy as np
+
+    import importlib.util
+
+    import torch
+
+    spec = importlib.util.spec_from_file_location(
+        "_bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    cap = bench.DUMP_BUDGET_BYTES // 4
+    assert bench.DUMP_BUDGET_BYTES <= 64 << 20
+    big = torch.arange(cap + 1000, dtype=torch.float32)
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), [("median", big)], 0, 1)
+    a = np.load(tmp_path / "a" / "median.npy")
+    assert a.dtype == np.float32 and a.shape == (cap,)
+    # values are their own coordinates: sorted, in range, spread over the
+    # whole output, and the same coordinates on every call
+    assert (np.diff(a) >= 0).all() and a[0] >= 0 and a[-1] < cap + 1000
+    assert a[-1] - a[0] > 0.99 * cap
+    assert np.array_equal(a, np.load(tmp_path / "b" / "median.npy"))
+
+
 def test_run_suite_single_workload():
     r = _run(
         ["benchmarks/run_suite.py", "--only", "Median n=64", "--repeat", "1",
