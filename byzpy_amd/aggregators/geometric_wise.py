@@ -57,15 +57,8 @@ class MultiKrum(Aggregator):
         X, like, handles = ctx.metadata.pop("_op_pending")
         try:
             G = torch.cat(results, dim=0)
-            norms = torch.diagonal(G)
-            D2 = (norms[:, None] + norms[None, :] - 2.0 * G).clamp_(min=0.0)
-            n = X.shape[0]
-            D2 = D2 + torch.diag(torch.full((n,), float("inf")))
-            k = n - self.f - 1
-            scores = torch.topk(D2, k=k, dim=1, largest=False).values.sum(dim=1)
-            winners = torch.topk(scores, k=self.q, largest=False).indices
-            out = X.float()[winners].mean(dim=0).to(X.dtype)
-            return to_like(out, like)
+            winners = D.krum_winners_from_gram(G, self.f, self.q)
+            return to_like(D.mean_rows(X, winners), like)
         finally:
             self._cleanup(handles)
 
@@ -84,13 +77,7 @@ class Krum(MultiKrum):
     def reduce_subtasks(self, ctx: OpContext, results: List[Any], **inputs: Any) -> Any:
         X, like, handles = ctx.metadata.pop("_op_pending")
         try:
-            G = torch.cat(results, dim=0)
-            norms = torch.diagonal(G)
-            D2 = (norms[:, None] + norms[None, :] - 2.0 * G).clamp_(min=0.0)
-            n = X.shape[0]
-            D2 = D2 + torch.diag(torch.full((n,), float("inf")))
-            k = n - self.f - 1
-            scores = torch.topk(D2, k=k, dim=1, largest=False).values.sum(dim=1)
+            scores = D.krum_scores_from_gram(torch.cat(results, dim=0), self.f)
             return to_like(X[int(torch.argmin(scores))].clone(), like)
         finally:
             self._cleanup(handles)

@@ -20,7 +20,8 @@ OUT_SO = PKG_DIR / "_hip_ops.so"
 BUILD_DIR = PKG_DIR.parent / "build" / "hip"
 
 SOURCES = ["colsel.hip", "rsel.hip", "rowops.hip", "gram.hip", "krumsel.hip",
-           "subsets.hip", "attacks.hip", "bind.cpp"]
+           "subsets.hip", "attacks.hip", "mda_host.cpp", "bind.cpp"]
+HEADERS = ["common.h", "launchers.h", "mda_host.h"]
 
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
@@ -44,7 +45,7 @@ def needs_rebuild() -> bool:
     if not OUT_SO.exists():
         return True
     so_mtime = OUT_SO.stat().st_mtime
-    for src in SOURCES + ["common.h", "build.py"]:
+    for src in SOURCES + HEADERS + ["build.py"]:
         p = CSRC / src if (CSRC / src).exists() else Path(__file__)
         if p.exists() and p.stat().st_mtime > so_mtime:
             return True

@@ -11,6 +11,7 @@
 // shape; it is a DIFFERENT sequence than torch's CPU generator (the
 // seeded-CPU contract stays available through the functional path).
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 
@@ -120,11 +121,6 @@ void launch_little(const T* X, T* out, int n, long d, float z,
   hipLaunchKernelGGL(little_kernel<T>, dim3(grid), dim3(block), 0, stream, X,
                      out, n, d, z);
 }
-template void launch_little<float>(const float*, float*, int, long, float,
-                                   hipStream_t);
-template void launch_little<__hip_bfloat16>(const __hip_bfloat16*,
-                                            __hip_bfloat16*, int, long, float,
-                                            hipStream_t);
 
 template <typename T>
 void launch_gaussian_fill(T* out, long d, unsigned long long seed, float mu,
@@ -136,8 +132,6 @@ void launch_gaussian_fill(T* out, long d, unsigned long long seed, float mu,
   hipLaunchKernelGGL(gaussian_fill_kernel<T>, dim3(grid), dim3(block), 0,
                      stream, out, d, (u32)seed, (u32)(seed >> 32), mu, sigma);
 }
-template void launch_gaussian_fill<float>(float*, long, unsigned long long,
-                                          float, float, hipStream_t);
-template void launch_gaussian_fill<__hip_bfloat16>(__hip_bfloat16*, long,
-                                                   unsigned long long, float,
-                                                   float, hipStream_t);
+
+INSTANTIATE_LAUNCHER(launch_little)
+INSTANTIATE_LAUNCHER(launch_gaussian_fill)

@@ -1,85 +1,19 @@
 // Python bindings for the byzpy_amd gfx950 kernel library.
-// Built in-tree by setup.py with explicit hipcc (no hipify, no CUDA shims).
+// Built in-tree by hip/build.py with explicit hipcc (no hipify, no CUDA
+// shims). Each op: validate, allocate, launch on the current stream.
 #include <torch/extension.h>
-#include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
 #include <c10/hip/HIPStream.h>
 
-#include <algorithm>
-#include <functional>
-#include <limits>
 #include <vector>
 
-// launchers (colsel.hip, rowops.hip, gram.hip)
-void launch_colsel_f32(const float*, float*, int, long, int, int, hipStream_t);
-void launch_colsel_bf16(const __hip_bfloat16*, __hip_bfloat16*, int, long, int,
-                        int, hipStream_t);
-template <typename T>
-void launch_row_sqnorms(const T*, float*, int, long, hipStream_t);
-template <typename T>
-void launch_row_center_sqdists(const T*, const float*, float*, int, long,
-                               hipStream_t);
-template <typename T>
-void launch_row_scale(const T*, const float*, T*, int, long, hipStream_t);
-template <typename T>
-void launch_mean_rows(const T*, const int*, int, T*, long, hipStream_t);
-template <typename T>
-void launch_group_mean_rows(const T*, const int*, int, int, T*, long,
-                            hipStream_t);
-template <typename T>
-void launch_bucket_mean(const T*, const int*, int, int, int, T*, long,
-                        hipStream_t);
-template <typename T>
-void launch_weiszfeld_update(const T*, const float*, const float*, float*,
-                             float*, int, long, float, hipStream_t);
-template <typename T>
-void launch_grouped_weiszfeld(const T*, const float*, float*, float*, int,
-                              int, long, float, hipStream_t);
-template <typename T>
-void launch_cc_update(const T*, const float*, const float*, float*, int, long,
-                      float, float, hipStream_t);
-// rsel.hip: generic multi-pass radix-select for the other large-n modes
-void launch_rsel_trimmed_bf16(const __hip_bfloat16*, __hip_bfloat16*,
-                              unsigned int*, int, long, int, hipStream_t);
-void launch_rsel_trimmed_f32(const float*, float*, unsigned int*, int, long,
-                             int, hipStream_t);
-void launch_rsel_median_f32(const float*, float*, unsigned int*, int, long,
-                            hipStream_t);
-void launch_rsel_median_bf16(const __hip_bfloat16*, __hip_bfloat16*,
-                             unsigned int*, int, long, hipStream_t);
-void launch_rsel_meamed_bf16(const __hip_bfloat16*, __hip_bfloat16*,
-                             unsigned int*, float*, int, long, int,
-                             hipStream_t);
-void launch_rsel_meamed_f32(const float*, float*, unsigned int*, float*, int,
-                            long, int, hipStream_t);
-template <typename T>
-void launch_caf_matvec(const T*, const float*, const float*, float*, int, long,
-                       hipStream_t);
-template <typename T>
-void launch_caf_colsum(const T*, const float*, const float*, const float*,
-                       float*, int, long, hipStream_t);
-// attacks.hip: K14 attack math
-template <typename T>
-void launch_little(const T*, T*, int, long, float, hipStream_t);
-template <typename T>
-void launch_gaussian_fill(T*, long, unsigned long long, float, float,
-                          hipStream_t);
-// subsets.hip: device-side exact subset searches (K11)
-void launch_smea_select(const float*, const int*, int, int, int,
-                        unsigned long long*, hipStream_t);
-void launch_mda_pass1(const float*, const int*, int, int, int, int,
-                      unsigned int*, hipStream_t);
-void launch_mda_pass2(const float*, const int*, int, int, int, int,
-                      unsigned int*, int*, int*, hipStream_t);
-void launch_gram_bf16(const __hip_bfloat16*, float*, int, long, hipStream_t);
-void launch_gram_f32(const float*, float*, int, long, hipStream_t);
-void launch_krum_select(const float*, int, int, int, int*, float*, hipStream_t);
+#include "launchers.h"
+#include "mda_host.h"
 
 namespace {
 
 hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
 
-constexpr int kMaxRowsLds = 1024;  // per-row weight staging in rowops LDS
+// -- argument checks --------------------------------------------------------
 
 void check_matrix(const torch::Tensor& X) {
   TORCH_CHECK(X.is_cuda(), "expected a device tensor");
@@ -90,12 +24,69 @@ void check_matrix(const torch::Tensor& X) {
               "expected f32 or bf16");
 }
 
-const __hip_bfloat16* bf16_ptr(const torch::Tensor& t) {
-  return reinterpret_cast<const __hip_bfloat16*>(t.data_ptr());
+void check_f32_vector(const torch::Tensor& t, int64_t len, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 &&
+                  t.is_contiguous() && t.numel() == len,
+              name, ": expected an f32 contiguous device vector of length ",
+              len);
 }
-__hip_bfloat16* bf16_ptr_mut(torch::Tensor& t) {
-  return reinterpret_cast<__hip_bfloat16*>(t.data_ptr());
+
+void check_f32_scalar(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 &&
+                  t.numel() == 1,
+              name, ": expected an f32 device scalar");
 }
+
+// int32 contiguous device tensor with `ndim` dimensions
+void check_i32(const torch::Tensor& t, int64_t ndim, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kInt32 &&
+                  t.is_contiguous() && t.dim() == ndim,
+              name, ": expected an int32 contiguous device tensor with ", ndim,
+              " dim(s)");
+}
+
+void check_gram(const torch::Tensor& G, const char* name) {
+  TORCH_CHECK(G.is_cuda() && G.dim() == 2 && G.size(0) == G.size(1) &&
+                  G.scalar_type() == torch::kFloat32 && G.is_contiguous(),
+              name, ": expected a square f32 contiguous device matrix");
+}
+
+// weiszfeld_update / cc_update / caf_colsum stage one weight per row in a
+// MAX_N_LDS-float LDS array; a larger n would write past it. Call before
+// any allocation or launch.
+void check_rows_fit_lds(int64_t n, const char* op) {
+  TORCH_CHECK(n <= MAX_N_LDS, op, " supports n <= ", MAX_N_LDS, ", got ", n);
+}
+
+// -- dtype dispatch ---------------------------------------------------------
+
+template <typename T>
+struct dtype_tag { using type = T; };
+
+// Calls fn(dtype_tag<T>) with T = float or __hip_bfloat16 after X's dtype
+// (check_matrix has already rejected everything else).
+template <typename F>
+void by_dtype(const torch::Tensor& X, F&& fn) {
+  if (X.scalar_type() == torch::kFloat32)
+    fn(dtype_tag<float>{});
+  else
+    fn(dtype_tag<__hip_bfloat16>{});
+}
+#define TAG_T(tag) typename decltype(tag)::type
+
+template <typename T>
+T* ptr(const torch::Tensor& t) { return reinterpret_cast<T*>(t.data_ptr()); }
+float* f32(const torch::Tensor& t) { return t.data_ptr<float>(); }
+int* i32(const torch::Tensor& t) { return t.data_ptr<int>(); }
+
+torch::TensorOptions f32_like(const torch::Tensor& X) {
+  return X.options().dtype(torch::kFloat32);
+}
+torch::TensorOptions i32_like(const torch::Tensor& X) {
+  return X.options().dtype(torch::kInt32);
+}
+
+// -- ops --------------------------------------------------------------------
 
 torch::Tensor colsel(torch::Tensor X, int64_t mode, int64_t f) {
   check_matrix(X);
@@ -111,44 +102,25 @@ torch::Tensor colsel(torch::Tensor X, int64_t mode, int64_t f) {
   TORCH_CHECK(n >= 1 && (n <= 512 || radix_ok),
               "colsel supports 1 <= n <= 65535, got ", n);
   TORCH_CHECK(f >= 0 && 2 * f < n, "bad f for colsel");
-  auto out = torch::empty({(long)d}, X.options());
-  if (radix_ok) {
-    const bool bf16 = X.scalar_type() == torch::kBFloat16;
-    // generic multi-pass engine (rsel.hip): per-column state scratch
-    auto state = torch::zeros({(long)d * 4}, X.options().dtype(torch::kInt32));
-    auto* st = reinterpret_cast<unsigned int*>(state.data_ptr<int>());
-    if (mode == 0 && bf16) {
-      launch_rsel_median_bf16(bf16_ptr(X), bf16_ptr_mut(out), st, n, d,
-                              cur_stream());
-    } else if (mode == 0) {  // f32 MEDIAN
-      launch_rsel_median_f32(X.data_ptr<float>(), out.data_ptr<float>(), st,
-                             n, d, cur_stream());
-    } else if (mode == 1) {
-      if (bf16)
-        launch_rsel_trimmed_bf16(bf16_ptr(X), bf16_ptr_mut(out), st, n, d,
-                                 (int)f, cur_stream());
-      else
-        launch_rsel_trimmed_f32(X.data_ptr<float>(), out.data_ptr<float>(),
-                                st, n, d, (int)f, cur_stream());
-    } else {
-      auto med = torch::empty({(long)d}, X.options().dtype(torch::kFloat32));
-      if (bf16)
-        launch_rsel_meamed_bf16(bf16_ptr(X), bf16_ptr_mut(out), st,
-                                med.data_ptr<float>(), n, d, (int)f,
-                                cur_stream());
-      else
-        launch_rsel_meamed_f32(X.data_ptr<float>(), out.data_ptr<float>(), st,
-                               med.data_ptr<float>(), n, d, (int)f,
-                               cur_stream());
-    }
+  auto out = torch::empty({d}, X.options());
+  if (!radix_ok) {
+    by_dtype(X, [&](auto tag) {
+      using T = TAG_T(tag);
+      launch_colsel<T>(ptr<T>(X), ptr<T>(out), n, d, (int)mode, (int)f,
+                       cur_stream());
+    });
     return out;
   }
-  if (X.scalar_type() == torch::kFloat32)
-    launch_colsel_f32(X.data_ptr<float>(), out.data_ptr<float>(), n, d,
-                      (int)mode, (int)f, cur_stream());
-  else
-    launch_colsel_bf16(bf16_ptr(X), bf16_ptr_mut(out), n, d, (int)mode, (int)f,
-                       cur_stream());
+  // generic multi-pass engine (rsel.hip): per-column state scratch, plus
+  // a median buffer for mean-around-median
+  auto state = torch::zeros({d * 4}, i32_like(X));
+  torch::Tensor med;
+  if (mode == 2) med = torch::empty({d}, f32_like(X));
+  by_dtype(X, [&](auto tag) {
+    using T = TAG_T(tag);
+    launch_rsel<T>((int)mode, ptr<T>(X), ptr<T>(out), ptr<unsigned int>(state),
+                   mode == 2 ? f32(med) : nullptr, n, d, (int)f, cur_stream());
+  });
   return out;
 }
 
@@ -156,101 +128,85 @@ torch::Tensor row_sqnorms(torch::Tensor X) {
   check_matrix(X);
   const int n = (int)X.size(0);
   const long d = (long)X.size(1);
-  auto out = torch::zeros({n}, X.options().dtype(torch::kFloat32));
-  if (X.scalar_type() == torch::kFloat32)
-    launch_row_sqnorms<float>(X.data_ptr<float>(), out.data_ptr<float>(), n, d,
-                              cur_stream());
-  else
-    launch_row_sqnorms<__hip_bfloat16>(bf16_ptr(X), out.data_ptr<float>(), n,
-                                       d, cur_stream());
+  auto out = torch::zeros({n}, f32_like(X));
+  by_dtype(X, [&](auto tag) {
+    using T = TAG_T(tag);
+    launch_row_sqnorms<T>(ptr<T>(X), f32(out), n, d, cur_stream());
+  });
   return out;
 }
 
 torch::Tensor row_center_sqdists(torch::Tensor X, torch::Tensor z) {
   check_matrix(X);
-  TORCH_CHECK(z.is_cuda() && z.scalar_type() == torch::kFloat32 &&
-              z.is_contiguous() && z.numel() == X.size(1));
   const int n = (int)X.size(0);
   const long d = (long)X.size(1);
-  auto out = torch::zeros({n}, X.options().dtype(torch::kFloat32));
-  if (X.scalar_type() == torch::kFloat32)
-    launch_row_center_sqdists<float>(X.data_ptr<float>(), z.data_ptr<float>(),
-                                     out.data_ptr<float>(), n, d, cur_stream());
-  else
-    launch_row_center_sqdists<__hip_bfloat16>(bf16_ptr(X), z.data_ptr<float>(),
-                                              out.data_ptr<float>(), n, d,
-                                              cur_stream());
+  check_f32_vector(z, d, "z");
+  auto out = torch::zeros({n}, f32_like(X));
+  by_dtype(X, [&](auto tag) {
+    using T = TAG_T(tag);
+    launch_row_center_sqdists<T>(ptr<T>(X), f32(z), f32(out), n, d,
+                                 cur_stream());
+  });
   return out;
 }
 
 torch::Tensor row_scale(torch::Tensor X, torch::Tensor s) {
   check_matrix(X);
-  TORCH_CHECK(s.is_cuda() && s.scalar_type() == torch::kFloat32 &&
-              s.is_contiguous() && s.numel() == X.size(0));
   const int n = (int)X.size(0);
   const long d = (long)X.size(1);
+  check_f32_vector(s, n, "s");
   auto out = torch::empty_like(X);
-  if (X.scalar_type() == torch::kFloat32)
-    launch_row_scale<float>(X.data_ptr<float>(), s.data_ptr<float>(),
-                            out.data_ptr<float>(), n, d, cur_stream());
-  else
-    launch_row_scale<__hip_bfloat16>(bf16_ptr(X), s.data_ptr<float>(),
-                                     bf16_ptr_mut(out), n, d, cur_stream());
+  by_dtype(X, [&](auto tag) {
+    using T = TAG_T(tag);
+    launch_row_scale<T>(ptr<T>(X), f32(s), ptr<T>(out), n, d, cur_stream());
+  });
   return out;
 }
 
 torch::Tensor mean_rows(torch::Tensor X, torch::Tensor idx) {
   check_matrix(X);
-  TORCH_CHECK(idx.is_cuda() && idx.scalar_type() == torch::kInt32 &&
-              idx.is_contiguous() && idx.dim() == 1 && idx.numel() >= 1);
+  check_i32(idx, 1, "idx");
+  TORCH_CHECK(idx.numel() >= 1, "idx: expected at least one row");
   const long d = (long)X.size(1);
   const int k = (int)idx.numel();
   auto out = torch::empty({d}, X.options());
-  if (X.scalar_type() == torch::kFloat32)
-    launch_mean_rows<float>(X.data_ptr<float>(), idx.data_ptr<int>(), k,
-                            out.data_ptr<float>(), d, cur_stream());
-  else
-    launch_mean_rows<__hip_bfloat16>(bf16_ptr(X), idx.data_ptr<int>(), k,
-                                     bf16_ptr_mut(out), d, cur_stream());
+  by_dtype(X, [&](auto tag) {
+    using T = TAG_T(tag);
+    launch_mean_rows<T>(ptr<T>(X), i32(idx), k, ptr<T>(out), d, cur_stream());
+  });
   return out;
 }
 
 torch::Tensor group_mean_rows(torch::Tensor X, torch::Tensor idx) {
   check_matrix(X);
-  TORCH_CHECK(idx.is_cuda() && idx.scalar_type() == torch::kInt32 &&
-              idx.is_contiguous() && idx.dim() == 2);
+  check_i32(idx, 2, "idx");
   const long d = (long)X.size(1);
   const int g = (int)idx.size(0);
   const int k = (int)idx.size(1);
   auto out = torch::empty({g, d}, X.options());
-  if (X.scalar_type() == torch::kFloat32)
-    launch_group_mean_rows<float>(X.data_ptr<float>(), idx.data_ptr<int>(), g,
-                                  k, out.data_ptr<float>(), d, cur_stream());
-  else
-    launch_group_mean_rows<__hip_bfloat16>(bf16_ptr(X), idx.data_ptr<int>(), g,
-                                           k, bf16_ptr_mut(out), d,
-                                           cur_stream());
+  by_dtype(X, [&](auto tag) {
+    using T = TAG_T(tag);
+    launch_group_mean_rows<T>(ptr<T>(X), i32(idx), g, k, ptr<T>(out), d,
+                              cur_stream());
+  });
   return out;
 }
 
 torch::Tensor bucket_mean(torch::Tensor X, torch::Tensor perm,
                           int64_t bucket) {
   check_matrix(X);
-  TORCH_CHECK(perm.is_cuda() && perm.scalar_type() == torch::kInt32 &&
-              perm.is_contiguous() && perm.numel() == X.size(0));
-  TORCH_CHECK(bucket >= 1);
   const int n = (int)X.size(0);
   const long d = (long)X.size(1);
+  check_i32(perm, 1, "perm");
+  TORCH_CHECK(perm.numel() == n, "perm: expected one entry per row");
+  TORCH_CHECK(bucket >= 1);
   const int nb = (int)((n + bucket - 1) / bucket);
   auto out = torch::empty({nb, d}, X.options());
-  if (X.scalar_type() == torch::kFloat32)
-    launch_bucket_mean<float>(X.data_ptr<float>(), perm.data_ptr<int>(), n,
-                              (int)bucket, nb, out.data_ptr<float>(), d,
-                              cur_stream());
-  else
-    launch_bucket_mean<__hip_bfloat16>(bf16_ptr(X), perm.data_ptr<int>(), n,
-                                       (int)bucket, nb, bf16_ptr_mut(out), d,
-                                       cur_stream());
+  by_dtype(X, [&](auto tag) {
+    using T = TAG_T(tag);
+    launch_bucket_mean<T>(ptr<T>(X), i32(perm), n, (int)bucket, nb,
+                          ptr<T>(out), d, cur_stream());
+  });
   return out;
 }
 
@@ -258,64 +214,59 @@ torch::Tensor gram(torch::Tensor X) {
   check_matrix(X);
   const int n = (int)X.size(0);
   const long d = (long)X.size(1);
-  auto G = torch::zeros({n, n}, X.options().dtype(torch::kFloat32));
-  if (X.scalar_type() == torch::kFloat32)
-    launch_gram_f32(X.data_ptr<float>(), G.data_ptr<float>(), n, d,
-                    cur_stream());
-  else
-    launch_gram_bf16(bf16_ptr(X), G.data_ptr<float>(), n, d, cur_stream());
+  auto G = torch::zeros({n, n}, f32_like(X));
+  by_dtype(X, [&](auto tag) {
+    using T = TAG_T(tag);
+    launch_gram<T>(ptr<T>(X), f32(G), n, d, cur_stream());
+  });
   return G;
-}
-
-// One Weiszfeld iteration: dist pass + fused update; accumulates ||dz||^2
-// into `shift` (callers poll it every few iterations — no per-iter sync).
-torch::Tensor weiszfeld_iter(torch::Tensor X, torch::Tensor z, double eps,
-                             torch::Tensor shift) {
-  check_matrix(X);
-  TORCH_CHECK(z.is_cuda() && z.scalar_type() == torch::kFloat32 &&
-              z.is_contiguous() && z.numel() == X.size(1));
-  TORCH_CHECK(shift.is_cuda() && shift.scalar_type() == torch::kFloat32 &&
-              shift.numel() == 1);
-  TORCH_CHECK(X.size(0) <= kMaxRowsLds, "weiszfeld supports n <= 1024");
-  const int n = (int)X.size(0);
-  const long d = (long)X.size(1);
-  auto dist2 = torch::zeros({n}, X.options().dtype(torch::kFloat32));
-  auto z_new = torch::empty_like(z);
-  shift.zero_();
-  if (X.scalar_type() == torch::kFloat32) {
-    launch_row_center_sqdists<float>(X.data_ptr<float>(), z.data_ptr<float>(),
-                                     dist2.data_ptr<float>(), n, d,
-                                     cur_stream());
-    launch_weiszfeld_update<float>(X.data_ptr<float>(), z.data_ptr<float>(),
-                                   dist2.data_ptr<float>(),
-                                   z_new.data_ptr<float>(),
-                                   shift.data_ptr<float>(), n, d, (float)eps,
-                                   cur_stream());
-  } else {
-    launch_row_center_sqdists<__hip_bfloat16>(
-        bf16_ptr(X), z.data_ptr<float>(), dist2.data_ptr<float>(), n, d,
-        cur_stream());
-    launch_weiszfeld_update<__hip_bfloat16>(
-        bf16_ptr(X), z.data_ptr<float>(), dist2.data_ptr<float>(),
-        z_new.data_ptr<float>(), shift.data_ptr<float>(), n, d, (float)eps,
-        cur_stream());
-  }
-  return z_new;
 }
 
 // Fused Krum selection: Gram -> q winner indices (one kernel, replaces
 // the D2-build + two topk torch chains whose launch overhead caps the
 // d-sharded multi-GPU scaling).
 torch::Tensor krum_select(torch::Tensor G, int64_t f, int64_t q) {
-  TORCH_CHECK(G.is_cuda() && G.dim() == 2 && G.size(0) == G.size(1) &&
-              G.scalar_type() == torch::kFloat32 && G.is_contiguous());
+  check_gram(G, "G");
   const int n = (int)G.size(0);
   TORCH_CHECK(n <= 512, "krum_select supports n <= 512");
   TORCH_CHECK(q >= 1 && q <= n && f >= 0 && n - f - 1 >= 1);
-  auto idx = torch::empty({q}, G.options().dtype(torch::kInt32));
-  launch_krum_select(G.data_ptr<float>(), n, (int)f, (int)q,
-                     idx.data_ptr<int>(), nullptr, cur_stream());
+  auto idx = torch::empty({q}, i32_like(G));
+  launch_krum_select(f32(G), n, (int)f, (int)q, i32(idx), nullptr,
+                     cur_stream());
   return idx;
+}
+
+// Sharded form of the Weiszfeld update: `dist2` holds the global squared
+// distances (multi-GPU d-sharding: all-reduced over RCCL). Accumulates
+// ||dz||^2 into `shift` (callers poll it every few iterations — no
+// per-iteration sync).
+torch::Tensor weiszfeld_apply(torch::Tensor X, torch::Tensor z,
+                              torch::Tensor dist2, double eps,
+                              torch::Tensor shift) {
+  check_matrix(X);
+  const int n = (int)X.size(0);
+  const long d = (long)X.size(1);
+  check_rows_fit_lds(n, "weiszfeld_apply");
+  check_f32_vector(z, d, "z");
+  check_f32_vector(dist2, n, "dist2");
+  check_f32_scalar(shift, "shift");
+  auto z_new = torch::empty_like(z);
+  shift.zero_();
+  by_dtype(X, [&](auto tag) {
+    using T = TAG_T(tag);
+    launch_weiszfeld_update<T>(ptr<T>(X), f32(z), f32(dist2), f32(z_new),
+                               f32(shift), n, d, (float)eps, cur_stream());
+  });
+  return z_new;
+}
+
+// One Weiszfeld iteration: distance pass + the fused update above.
+torch::Tensor weiszfeld_iter(torch::Tensor X, torch::Tensor z, double eps,
+                             torch::Tensor shift) {
+  check_matrix(X);
+  check_rows_fit_lds(X.size(0), "weiszfeld_iter");
+  check_f32_scalar(shift, "shift");
+  return weiszfeld_apply(X, z, row_center_sqdists(X, z), eps, shift);
 }
 
 // Grouped Weiszfeld iteration: G independent (m, d) problems, one kernel
@@ -331,202 +282,41 @@ torch::Tensor weiszfeld_iter_grouped(torch::Tensor X3, torch::Tensor Z,
   const int m = (int)X3.size(1);
   const long d = (long)X3.size(2);
   TORCH_CHECK(m >= 1 && m <= 32, "grouped weiszfeld supports m <= 32");
-  TORCH_CHECK(Z.is_cuda() && Z.scalar_type() == torch::kFloat32 &&
-              Z.is_contiguous() && Z.dim() == 2 && Z.size(0) == G &&
-              Z.size(1) == d);
-  auto dist2 = torch::zeros({G, (long)m},
-                            X3.options().dtype(torch::kFloat32));
+  check_f32_vector(Z, (int64_t)G * d, "Z");
+  TORCH_CHECK(Z.dim() == 2 && Z.size(0) == G, "Z: expected (G, d)");
+  auto dist2 = torch::zeros({G, m}, f32_like(X3));
   auto Z_new = torch::empty_like(Z);
-  if (X3.scalar_type() == torch::kFloat32)
-    launch_grouped_weiszfeld<float>(X3.data_ptr<float>(), Z.data_ptr<float>(),
-                                    dist2.data_ptr<float>(),
-                                    Z_new.data_ptr<float>(), G, m, d,
-                                    (float)eps, cur_stream());
-  else
-    launch_grouped_weiszfeld<__hip_bfloat16>(
-        bf16_ptr(X3), Z.data_ptr<float>(), dist2.data_ptr<float>(),
-        Z_new.data_ptr<float>(), G, m, d, (float)eps, cur_stream());
+  by_dtype(X3, [&](auto tag) {
+    using T = TAG_T(tag);
+    launch_grouped_weiszfeld<T>(ptr<T>(X3), f32(Z), f32(dist2), f32(Z_new), G,
+                                m, d, (float)eps, cur_stream());
+  });
   return Z_new;
 }
 
-// Sharded form: apply the Weiszfeld update with externally-reduced global
-// distances (multi-GPU d-sharding: dist2 was all-reduced over RCCL).
-torch::Tensor weiszfeld_apply(torch::Tensor X, torch::Tensor z,
-                              torch::Tensor dist2, double eps,
-                              torch::Tensor shift) {
-  check_matrix(X);
-  const int n = (int)X.size(0);
-  const long d = (long)X.size(1);
-  TORCH_CHECK(dist2.is_cuda() && dist2.scalar_type() == torch::kFloat32 &&
-              dist2.numel() == n);
-  auto z_new = torch::empty_like(z);
-  shift.zero_();
-  if (X.scalar_type() == torch::kFloat32)
-    launch_weiszfeld_update<float>(X.data_ptr<float>(), z.data_ptr<float>(),
-                                   dist2.data_ptr<float>(),
-                                   z_new.data_ptr<float>(),
-                                   shift.data_ptr<float>(), n, d, (float)eps,
-                                   cur_stream());
-  else
-    launch_weiszfeld_update<__hip_bfloat16>(
-        bf16_ptr(X), z.data_ptr<float>(), dist2.data_ptr<float>(),
-        z_new.data_ptr<float>(), shift.data_ptr<float>(), n, d, (float)eps,
-        cur_stream());
-  return z_new;
-}
-
+// Sharded form of the centered-clipping update (dist2 reduced externally).
 torch::Tensor cc_apply(torch::Tensor X, torch::Tensor v, torch::Tensor dist2,
                        double c_tau, double eps) {
   check_matrix(X);
   const int n = (int)X.size(0);
   const long d = (long)X.size(1);
-  TORCH_CHECK(dist2.is_cuda() && dist2.scalar_type() == torch::kFloat32 &&
-              dist2.numel() == n);
+  check_rows_fit_lds(n, "cc_apply");
+  check_f32_vector(v, d, "v");
+  check_f32_vector(dist2, n, "dist2");
   auto v_new = torch::empty_like(v);
-  if (X.scalar_type() == torch::kFloat32)
-    launch_cc_update<float>(X.data_ptr<float>(), v.data_ptr<float>(),
-                            dist2.data_ptr<float>(), v_new.data_ptr<float>(),
-                            n, d, (float)c_tau, (float)eps, cur_stream());
-  else
-    launch_cc_update<__hip_bfloat16>(bf16_ptr(X), v.data_ptr<float>(),
-                                     dist2.data_ptr<float>(),
-                                     v_new.data_ptr<float>(), n, d,
-                                     (float)c_tau, (float)eps, cur_stream());
+  by_dtype(X, [&](auto tag) {
+    using T = TAG_T(tag);
+    launch_cc_update<T>(ptr<T>(X), f32(v), f32(dist2), f32(v_new), n, d,
+                        (float)c_tau, (float)eps, cur_stream());
+  });
   return v_new;
 }
 
 torch::Tensor cc_iter(torch::Tensor X, torch::Tensor v, double c_tau,
                       double eps) {
   check_matrix(X);
-  TORCH_CHECK(X.size(0) <= kMaxRowsLds, "cc supports n <= 1024");
-  TORCH_CHECK(v.is_cuda() && v.scalar_type() == torch::kFloat32 &&
-              v.is_contiguous() && v.numel() == X.size(1));
-  const int n = (int)X.size(0);
-  const long d = (long)X.size(1);
-  auto dist2 = torch::zeros({n}, X.options().dtype(torch::kFloat32));
-  auto v_new = torch::empty_like(v);
-  if (X.scalar_type() == torch::kFloat32) {
-    launch_row_center_sqdists<float>(X.data_ptr<float>(), v.data_ptr<float>(),
-                                     dist2.data_ptr<float>(), n, d,
-                                     cur_stream());
-    launch_cc_update<float>(X.data_ptr<float>(), v.data_ptr<float>(),
-                            dist2.data_ptr<float>(), v_new.data_ptr<float>(),
-                            n, d, (float)c_tau, (float)eps, cur_stream());
-  } else {
-    launch_row_center_sqdists<__hip_bfloat16>(
-        bf16_ptr(X), v.data_ptr<float>(), dist2.data_ptr<float>(), n, d,
-        cur_stream());
-    launch_cc_update<__hip_bfloat16>(bf16_ptr(X), v.data_ptr<float>(),
-                                     dist2.data_ptr<float>(),
-                                     v_new.data_ptr<float>(), n, d,
-                                     (float)c_tau, (float)eps, cur_stream());
-  }
-  return v_new;
-}
-
-// Exact minimum-diameter (n-f)-subset search (MDA) — HOST code: the n x n
-// squared-distance matrix is tiny; the combinatorial DFS belongs in native
-// C++, not Python (reference ran a seeded-DFS process pool for this,
-// minimum_diameter_average.py:267-386). Branch-and-bound over candidates
-// ordered by greedy insertion cost, seeded with a greedy upper bound.
-torch::Tensor mda_search(torch::Tensor D2in, int64_t f) {
-  TORCH_CHECK(!D2in.is_cuda(), "mda_search runs on the host copy of D2");
-  auto D2 = D2in.to(torch::kFloat64).contiguous();
-  const int n = (int)D2.size(0);
-  const int m = n - (int)f;
-  TORCH_CHECK(m >= 1 && D2.size(1) == n);
-  auto D = D2.accessor<double, 2>();
-
-  // greedy seed: for each anchor row, grow the subset by min-added-diameter
-  double best_diam = std::numeric_limits<double>::infinity();
-  std::vector<int> best;
-  std::vector<int> cur;
-  std::vector<double> maxd(n);
-  for (int a = 0; a < n; ++a) {
-    cur.assign(1, a);
-    std::fill(maxd.begin(), maxd.end(), 0.0);
-    std::vector<char> used(n, 0);
-    used[a] = 1;
-    for (int j = 0; j < n; ++j) maxd[j] = D[a][j];
-    double diam = 0.0;
-    for (int step = 1; step < m; ++step) {
-      int pick = -1;
-      double pick_cost = std::numeric_limits<double>::infinity();
-      for (int j = 0; j < n; ++j)
-        if (!used[j] && maxd[j] < pick_cost) { pick_cost = maxd[j]; pick = j; }
-      used[pick] = 1;
-      cur.push_back(pick);
-      diam = std::max(diam, pick_cost);
-      for (int j = 0; j < n; ++j) maxd[j] = std::max(maxd[j], D[pick][j]);
-    }
-    if (diam < best_diam) { best_diam = diam; best = cur; }
-  }
-
-  // exact DFS with prefix-max pruning (candidates in greedy-friendly order)
-  std::vector<int> order(n);
-  for (int i = 0; i < n; ++i) order[i] = i;
-  // order by row-sum of distances: central rows first
-  std::vector<double> rowsum(n, 0.0);
-  for (int i = 0; i < n; ++i)
-    for (int j = 0; j < n; ++j) rowsum[i] += D[i][j];
-  std::sort(order.begin(), order.end(),
-            [&](int a, int b) { return rowsum[a] < rowsum[b]; });
-
-  std::vector<int> chosen;
-  chosen.reserve(m);
-  std::function<void(int, double)> dfs = [&](int start, double diam) {
-    if ((int)chosen.size() == m) {
-      if (diam < best_diam) { best_diam = diam; best = chosen; }
-      return;
-    }
-    const int need = m - (int)chosen.size();
-    for (int oi = start; oi <= n - need; ++oi) {
-      const int j = order[oi];
-      double dj = diam;
-      bool ok = true;
-      for (int c : chosen) {
-        const double dc = D[c][j];
-        if (dc >= best_diam) { ok = false; break; }
-        if (dc > dj) dj = dc;
-      }
-      if (!ok || dj >= best_diam) continue;
-      chosen.push_back(j);
-      dfs(oi + 1, dj);
-      chosen.pop_back();
-    }
-  };
-  dfs(0, 0.0);
-
-  // Canonicalize: among all subsets achieving best_diam, return the
-  // lexicographically smallest (optimal subsets are generically non-unique
-  // — every subset containing the binding edge ties). Pure index-order DFS
-  // with the now-tight bound; the first complete subset found is the
-  // lexicographic minimum.
-  const double bound = best_diam;
-  std::vector<int> lex;
-  lex.reserve(m);
-  bool found = false;
-  std::function<void(int)> dfs2 = [&](int start) {
-    if (found) return;
-    if ((int)lex.size() == m) { best = lex; found = true; return; }
-    const int need = m - (int)lex.size();
-    for (int j = start; j <= n - need && !found; ++j) {
-      bool ok = true;
-      for (int c : lex)
-        if (D[c][j] > bound) { ok = false; break; }
-      if (!ok) continue;
-      lex.push_back(j);
-      dfs2(j + 1);
-      lex.pop_back();
-    }
-  };
-  dfs2(0);
-
-  std::sort(best.begin(), best.end());
-  auto out = torch::empty({(long)best.size()}, torch::kInt64);
-  auto acc = out.accessor<int64_t, 1>();
-  for (size_t i = 0; i < best.size(); ++i) acc[i] = best[i];
-  return out;
+  check_rows_fit_lds(X.size(0), "cc_iter");
+  return cc_apply(X, v, row_center_sqdists(X, v), c_tau, eps);
 }
 
 // Little attack fused: per-column mu + z*sigma in one streaming pass.
@@ -535,12 +325,10 @@ torch::Tensor little_fused(torch::Tensor X, double z) {
   const int n = (int)X.size(0);
   const long d = (long)X.size(1);
   auto out = torch::empty({d}, X.options());
-  if (X.scalar_type() == torch::kFloat32)
-    launch_little<float>(X.data_ptr<float>(), out.data_ptr<float>(), n, d,
-                         (float)z, cur_stream());
-  else
-    launch_little<__hip_bfloat16>(bf16_ptr(X), bf16_ptr_mut(out), n, d,
-                                  (float)z, cur_stream());
+  by_dtype(X, [&](auto tag) {
+    using T = TAG_T(tag);
+    launch_little<T>(ptr<T>(X), ptr<T>(out), n, d, (float)z, cur_stream());
+  });
   return out;
 }
 
@@ -548,50 +336,43 @@ torch::Tensor little_fused(torch::Tensor X, double z) {
 torch::Tensor gaussian_fill(int64_t d, int64_t seed, double mu, double sigma,
                             torch::Tensor like) {
   TORCH_CHECK(like.is_cuda(), "gaussian_fill needs a device template");
+  TORCH_CHECK(like.scalar_type() == torch::kFloat32 ||
+                  like.scalar_type() == torch::kBFloat16,
+              "expected f32 or bf16");
   TORCH_CHECK(d >= 1);
   auto out = torch::empty({d}, like.options());
-  if (like.scalar_type() == torch::kFloat32)
-    launch_gaussian_fill<float>(out.data_ptr<float>(), d,
-                                (unsigned long long)seed, (float)mu,
-                                (float)sigma, cur_stream());
-  else
-    launch_gaussian_fill<__hip_bfloat16>(bf16_ptr_mut(out), d,
-                                         (unsigned long long)seed, (float)mu,
-                                         (float)sigma, cur_stream());
+  by_dtype(like, [&](auto tag) {
+    using T = TAG_T(tag);
+    launch_gaussian_fill<T>(ptr<T>(out), d, (unsigned long long)seed,
+                            (float)mu, (float)sigma, cur_stream());
+  });
   return out;
 }
 
 // SMEA subset selection fully on device (subsets.hip): returns the
 // winning combo INDEX packed in the low 32 bits of a u64 key tensor.
 torch::Tensor smea_select(torch::Tensor G, torch::Tensor combos) {
-  TORCH_CHECK(G.is_cuda() && G.dim() == 2 && G.size(0) == G.size(1) &&
-              G.scalar_type() == torch::kFloat32 && G.is_contiguous());
-  TORCH_CHECK(combos.is_cuda() && combos.dim() == 2 &&
-              combos.scalar_type() == torch::kInt32 && combos.is_contiguous());
+  check_gram(G, "G");
+  check_i32(combos, 2, "combos");
   const int n = (int)G.size(0);
   const int C = (int)combos.size(0);
   const int m = (int)combos.size(1);
   TORCH_CHECK(m >= 1 && m <= 64 && C >= 1);
   auto best = torch::full({1}, -1, G.options().dtype(torch::kInt64));
-  launch_smea_select(G.data_ptr<float>(), combos.data_ptr<int>(), n, m, C,
-                     reinterpret_cast<unsigned long long*>(
-                         best.data_ptr<int64_t>()),
-                     cur_stream());
+  launch_smea_select(f32(G), i32(combos), n, m, C,
+                     ptr<unsigned long long>(best), cur_stream());
   return best;
 }
 
 // MDA two-pass device search: returns (found[npairs], subsets[npairs, m]);
 // the first found prefix (pair-lex order) holds the lex-smallest optimal
 // subset. No host sync anywhere.
+// (A centrality-permuted pass-1 variant measured 15x SLOWER — central-first
+// lex order wanders near-optimal subtrees B&B cannot prune — so pass 1
+// walks prefixes in plain index order.)
 std::vector<torch::Tensor> mda_select(torch::Tensor D2, int64_t f,
-                                      c10::optional<torch::Tensor> ub,
-                                      c10::optional<torch::Tensor> D2perm) {
-  TORCH_CHECK(D2.is_cuda() && D2.dim() == 2 && D2.size(0) == D2.size(1) &&
-              D2.scalar_type() == torch::kFloat32 && D2.is_contiguous());
-  (void)D2perm;  // a centrality-permuted pass-1 variant measured 15x
-                 // SLOWER (central-first lex order wanders near-optimal
-                 // subtrees B&B cannot prune); kept in the signature for
-                 // call compatibility, ignored
+                                      c10::optional<torch::Tensor> ub) {
+  check_gram(D2, "D2");
   const int n = (int)D2.size(0);
   const int m = n - (int)f;
   TORCH_CHECK(n <= 64, "mda_select supports n <= 64");
@@ -634,28 +415,22 @@ std::vector<torch::Tensor> mda_select(torch::Tensor D2, int64_t f,
   // from the start (one ulp up so strict < can re-find an exact tie).
   torch::Tensor best;
   if (ub.has_value()) {
-    TORCH_CHECK(ub->is_cuda() && ub->scalar_type() == torch::kFloat32 &&
-                ub->numel() == 1);
+    check_f32_scalar(*ub, "ub");
     auto bits = torch::nan_to_num(ub.value(), 0.0, 3.0e38, 0.0)
                     .view(torch::kInt32);
     best = (bits + 1).bitwise_or((int)0x80000000).contiguous();
   } else {
-    best = torch::full({1}, (int)0xFF800000,
-                       D2.options().dtype(torch::kInt32));
+    best = torch::full({1}, (int)0xFF800000, i32_like(D2));
   }
-  auto subsets = torch::zeros({npre, (long)m},
-                              D2.options().dtype(torch::kInt32));
-  auto found = torch::zeros({npre}, D2.options().dtype(torch::kInt32));
-  auto* bp = reinterpret_cast<unsigned int*>(best.data_ptr<int>());
-  launch_mda_pass1(D2.data_ptr<float>(), prefixes.data_ptr<int>(), P, n, m,
-                   (int)npre, bp, cur_stream());
-  launch_mda_pass2(D2.data_ptr<float>(), prefixes.data_ptr<int>(), P, n, m,
-                   (int)npre, bp, subsets.data_ptr<int>(),
-                   found.data_ptr<int>(), cur_stream());
+  auto subsets = torch::zeros({npre, (long)m}, i32_like(D2));
+  auto found = torch::zeros({npre}, i32_like(D2));
+  auto* bp = ptr<unsigned int>(best);
+  launch_mda_pass1(f32(D2), i32(prefixes), P, n, m, (int)npre, bp,
+                   cur_stream());
+  launch_mda_pass2(f32(D2), i32(prefixes), P, n, m, (int)npre, bp,
+                   i32(subsets), i32(found), cur_stream());
   return {found, subsets};
 }
-
-}  // namespace
 
 // -- CAF fused power-iteration pair --------------------------
 
@@ -663,20 +438,14 @@ torch::Tensor caf_matvec(torch::Tensor X, torch::Tensor mu, torch::Tensor v) {
   check_matrix(X);
   const int n = (int)X.size(0);
   const long d = (long)X.size(1);
-  TORCH_CHECK(mu.is_cuda() && mu.scalar_type() == torch::kFloat32 &&
-              mu.is_contiguous() && mu.numel() == d);
-  TORCH_CHECK(v.is_cuda() && v.scalar_type() == torch::kFloat32 &&
-              v.is_contiguous() && v.numel() == d);
-  auto out = torch::zeros({n}, X.options().dtype(torch::kFloat32));
-  if (X.scalar_type() == torch::kFloat32)
-    launch_caf_matvec<float>(X.data_ptr<float>(), mu.data_ptr<float>(),
-                             v.data_ptr<float>(), out.data_ptr<float>(), n, d,
-                             cur_stream());
-  else
-    launch_caf_matvec<__hip_bfloat16>(bf16_ptr(X), mu.data_ptr<float>(),
-                                      v.data_ptr<float>(),
-                                      out.data_ptr<float>(), n, d,
-                                      cur_stream());
+  check_f32_vector(mu, d, "mu");
+  check_f32_vector(v, d, "v");
+  auto out = torch::zeros({n}, f32_like(X));
+  by_dtype(X, [&](auto tag) {
+    using T = TAG_T(tag);
+    launch_caf_matvec<T>(ptr<T>(X), f32(mu), f32(v), f32(out), n, d,
+                         cur_stream());
+  });
   return out;
 }
 
@@ -686,32 +455,22 @@ torch::Tensor caf_colsum(torch::Tensor X, torch::Tensor a,
   check_matrix(X);
   const int n = (int)X.size(0);
   const long d = (long)X.size(1);
-  TORCH_CHECK(n <= kMaxRowsLds, "caf_colsum supports n <= 1024");
-  TORCH_CHECK(a.is_cuda() && a.scalar_type() == torch::kFloat32 &&
-              a.is_contiguous() && a.numel() == n);
-  const float* mu_p = nullptr;
-  if (mu.has_value()) {
-    TORCH_CHECK(mu->is_cuda() && mu->scalar_type() == torch::kFloat32 &&
-                mu->is_contiguous() && mu->numel() == d);
-    mu_p = mu->data_ptr<float>();
-  }
-  const float* sc_p = nullptr;
-  if (scale.has_value()) {
-    TORCH_CHECK(scale->is_cuda() &&
-                scale->scalar_type() == torch::kFloat32 &&
-                scale->numel() == 1);
-    sc_p = scale->data_ptr<float>();
-  }
-  auto out = torch::empty({d}, X.options().dtype(torch::kFloat32));
-  if (X.scalar_type() == torch::kFloat32)
-    launch_caf_colsum<float>(X.data_ptr<float>(), a.data_ptr<float>(), mu_p,
-                             sc_p, out.data_ptr<float>(), n, d, cur_stream());
-  else
-    launch_caf_colsum<__hip_bfloat16>(bf16_ptr(X), a.data_ptr<float>(), mu_p,
-                                      sc_p, out.data_ptr<float>(), n, d,
-                                      cur_stream());
+  check_rows_fit_lds(n, "caf_colsum");
+  check_f32_vector(a, n, "a");
+  if (mu.has_value()) check_f32_vector(*mu, d, "mu");
+  if (scale.has_value()) check_f32_scalar(*scale, "scale");
+  const float* mu_p = mu.has_value() ? f32(*mu) : nullptr;
+  const float* sc_p = scale.has_value() ? f32(*scale) : nullptr;
+  auto out = torch::empty({d}, f32_like(X));
+  by_dtype(X, [&](auto tag) {
+    using T = TAG_T(tag);
+    launch_caf_colsum<T>(ptr<T>(X), f32(a), mu_p, sc_p, f32(out), n, d,
+                         cur_stream());
+  });
   return out;
 }
+
+}  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("colsel", &colsel, "columnwise median/trimmed-mean/meamed");
@@ -737,6 +496,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("little_fused", &little_fused, "fused Little attack (K14)");
   m.def("gaussian_fill", &gaussian_fill, "philox gaussian fill (K14)");
   m.def("mda_select", &mda_select, "device MDA two-pass B&B search (K11)",
-        py::arg("D2"), py::arg("f"), py::arg("ub") = c10::nullopt,
-        py::arg("D2perm") = c10::nullopt);
+        py::arg("D2"), py::arg("f"), py::arg("ub") = c10::nullopt);
 }

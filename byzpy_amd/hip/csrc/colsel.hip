@@ -18,7 +18,9 @@
 // Loads are coalesced: adjacent lanes read adjacent columns, so each
 // row-iteration is one 256 B (f32) / 128 B (bf16) wave transaction.
 #include "common.h"
+#include "launchers.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace {
 
@@ -682,6 +684,30 @@ colsel_lds_kernel(const T* __restrict__ X, T* __restrict__ out,
   }
 }
 
+// Turns the runtime mode / row count into the kernels' template arguments:
+// fn receives std::integral_constant<int, MODE> / <int, P>.
+template <typename F>
+inline void by_mode(int mode, F&& fn) {
+  if (mode == MEDIAN) fn(std::integral_constant<int, MEDIAN>{});
+  else if (mode == TRIMMED) fn(std::integral_constant<int, TRIMMED>{});
+  else fn(std::integral_constant<int, MEAMED>{});
+}
+
+// padded register width of the n <= 64 kernels
+template <typename F>
+inline void by_reg_width(int n, F&& fn) {
+  if (n <= 8) fn(std::integral_constant<int, 8>{});
+  else if (n <= 16) fn(std::integral_constant<int, 16>{});
+  else if (n <= 32) fn(std::integral_constant<int, 32>{});
+  else fn(std::integral_constant<int, 64>{});
+}
+
+// grid-stride launch width: one unit per thread, capped at 8192 blocks
+inline int capped_grid(long units, int block) {
+  const long want = (units + block - 1) / block;
+  return (int)(want < 8192 ? (want > 0 ? want : 1) : 8192);
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -689,51 +715,40 @@ colsel_lds_kernel(const T* __restrict__ X, T* __restrict__ out,
 // ---------------------------------------------------------------------------
 
 template <typename T>
-static void launch_colsel_typed(const T* X, T* out, int n, long d, int mode,
-                                int f, hipStream_t stream) {
-  if (n <= 64) {
-    const int block = 256;
-    const long want = (d + block - 1) / block;
-    const int grid = (int)(want < 8192 ? (want > 0 ? want : 1) : 8192);
-#define DISPATCH_ONE(P, MODE)                                                  \
-  hipLaunchKernelGGL((colsel_reg_kernel<P, MODE, T>), dim3(grid),              \
-                     dim3(block), 0, stream, X, out, n, d, f)
-#define DISPATCH_REG(P)                                                        \
-  do {                                                                         \
-    if (mode == MEDIAN) DISPATCH_ONE(P, MEDIAN);                               \
-    else if (mode == TRIMMED) DISPATCH_ONE(P, TRIMMED);                        \
-    else DISPATCH_ONE(P, MEAMED);                                              \
-  } while (0)
-    if (n <= 8) DISPATCH_REG(8);
-    else if (n <= 16) DISPATCH_REG(16);
-    else if (n <= 32) DISPATCH_REG(32);
-    else DISPATCH_REG(64);
-#undef DISPATCH_REG
-#undef DISPATCH_ONE
-  } else {
-    int P = 128;
-    while (P < n) P <<= 1;  // 128/256/512
-    const long grid = (d + LDS_COLS - 1) / LDS_COLS;
-    const size_t lds = (size_t)P * LDS_COLS * sizeof(float);
-    if (mode == MEDIAN)
-      hipLaunchKernelGGL((colsel_lds_kernel<MEDIAN, T>), dim3(grid),
+static void colsel_generic(const T* X, T* out, int n, long d, int mode, int f,
+                           hipStream_t stream) {
+  by_mode(mode, [&](auto m) {
+    constexpr int MODE = decltype(m)::value;
+    if (n <= 64) {
+      const int block = 256;
+      const int grid = capped_grid(d, block);
+      by_reg_width(n, [&](auto p) {
+        hipLaunchKernelGGL((colsel_reg_kernel<decltype(p)::value, MODE, T>),
+                           dim3(grid), dim3(block), 0, stream, X, out, n, d,
+                           f);
+      });
+    } else {
+      int P = 128;
+      while (P < n) P <<= 1;  // 128/256/512
+      const long grid = (d + LDS_COLS - 1) / LDS_COLS;
+      const size_t lds = (size_t)P * LDS_COLS * sizeof(float);
+      hipLaunchKernelGGL((colsel_lds_kernel<MODE, T>), dim3(grid),
                          dim3(LDS_THREADS), lds, stream, X, out, n, d, f, P);
-    else if (mode == TRIMMED)
-      hipLaunchKernelGGL((colsel_lds_kernel<TRIMMED, T>), dim3(grid),
-                         dim3(LDS_THREADS), lds, stream, X, out, n, d, f, P);
-    else
-      hipLaunchKernelGGL((colsel_lds_kernel<MEAMED, T>), dim3(grid),
-                         dim3(LDS_THREADS), lds, stream, X, out, n, d, f, P);
-  }
+    }
+  });
 }
 
-void launch_colsel_f32(const float* X, float* out, int n, long d, int mode,
-                       int f, hipStream_t stream) {
-  launch_colsel_typed<float>(X, out, n, d, mode, f, stream);
+template <>
+void launch_colsel<float>(const float* X, float* out, int n, long d, int mode,
+                          int f, hipStream_t stream) {
+  colsel_generic(X, out, n, d, mode, f, stream);
 }
 
-void launch_colsel_bf16(const __hip_bfloat16* X, __hip_bfloat16* out, int n,
-                        long d, int mode, int f, hipStream_t stream) {
+// bf16 with n <= 64 and even d takes the packed path (two columns per lane)
+template <>
+void launch_colsel<__hip_bfloat16>(const __hip_bfloat16* X,
+                                   __hip_bfloat16* out, int n, long d,
+                                   int mode, int f, hipStream_t stream) {
   if (n <= 64 && (d % 2) == 0) {
     const int block = 256;
     // A/B'd on MI355X: QUADS (8 B/lane) TIED the old full-sort variant
@@ -741,42 +756,30 @@ void launch_colsel_bf16(const __hip_bfloat16* X, __hip_bfloat16* out, int n,
     // pair variant (9.09 vs 3.09 ms — two 64-reg key arrays force the
     // 3-waves/SIMD bound while the pair kernel runs at 5). Single-pair
     // is the shipping path; BYZPY_PK_QUADS=1 re-runs the comparison.
-    const long units = d >> 1;
-    const long want = (units + block - 1) / block;
-    const int grid = (int)(want < 8192 ? (want > 0 ? want : 1) : 8192);
+    const int grid = capped_grid(d >> 1, block);
     const unsigned short* Xu = reinterpret_cast<const unsigned short*>(X);
     unsigned short* Ou = reinterpret_cast<unsigned short*>(out);
     // A/B aid: BYZPY_PK_QUADS=1 re-measures the 4-column (8 B/lane)
     // MEDIAN variant (tied pre-selection-network; see the comment above)
     if (mode == MEDIAN && n > 32 && (d % 4) == 0 &&
         std::getenv("BYZPY_PK_QUADS") != nullptr) {
-      const long qunits = d >> 2;
-      const long qwant = (qunits + block - 1) / block;
-      const int qgrid = (int)(qwant < 8192 ? (qwant > 0 ? qwant : 1) : 8192);
+      const int qgrid = capped_grid(d >> 2, block);
       hipLaunchKernelGGL((colsel_pk_median_bf16<64, true, MEDIAN>),
                          dim3(qgrid), dim3(block), 0, stream, Xu, Ou, n, d, f);
       return;
     }
-#define PK_LAUNCH(P)                                                          \
-  do {                                                                        \
-    if (mode == MEDIAN)                                                       \
-      hipLaunchKernelGGL((colsel_pk_median_bf16<P, false, MEDIAN>),           \
-                         dim3(grid), dim3(block), 0, stream, Xu, Ou, n, d, f);\
-    else if (mode == TRIMMED)                                                 \
-      hipLaunchKernelGGL((colsel_pk_median_bf16<P, false, TRIMMED>),          \
-                         dim3(grid), dim3(block), 0, stream, Xu, Ou, n, d, f);\
-    else                                                                      \
-      hipLaunchKernelGGL((colsel_pk_median_bf16<P, false, MEAMED>),           \
-                         dim3(grid), dim3(block),                             \
-                         (size_t)block * (2 * (f + 1) + 1) * sizeof(u32),     \
-                         stream, Xu, Ou, n, d, f);                            \
-  } while (0)
-    if (n <= 8) PK_LAUNCH(8);
-    else if (n <= 16) PK_LAUNCH(16);
-    else if (n <= 32) PK_LAUNCH(32);
-    else PK_LAUNCH(64);
-#undef PK_LAUNCH
+    by_mode(mode, [&](auto m) {
+      constexpr int MODE = decltype(m)::value;
+      // MEAMED stages a 2(f+1)-key strip per thread in LDS (odd stride)
+      const size_t lds =
+          MODE == MEAMED ? (size_t)block * (2 * (f + 1) + 1) * sizeof(u32) : 0;
+      by_reg_width(n, [&](auto p) {
+        hipLaunchKernelGGL(
+            (colsel_pk_median_bf16<decltype(p)::value, false, MODE>),
+            dim3(grid), dim3(block), lds, stream, Xu, Ou, n, d, f);
+      });
+    });
     return;
   }
-  launch_colsel_typed<__hip_bfloat16>(X, out, n, d, mode, f, stream);
+  colsel_generic(X, out, n, d, mode, f, stream);
 }

@@ -16,6 +16,7 @@
 //     f32 path: v_mfma_f32_16x16x4_f32 (exact f32 at the vector rate,
 //     guide §3 — no xf32 on gfx950).
 #include "common.h"
+#include "launchers.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -885,8 +886,9 @@ inline void split_geometry(int n, long d, int& splitk, long& k_per_block) {
 
 }  // namespace
 
-void launch_gram_bf16(const __hip_bfloat16* X, float* G, int n, long d,
-                      hipStream_t stream) {
+template <>
+void launch_gram<__hip_bfloat16>(const __hip_bfloat16* X, float* G, int n,
+                                 long d, hipStream_t stream) {
   if (n <= 32 && (d % 8) == 0 && d >= 64) {
     long kpw, blocks;
     if (n <= 16) {
@@ -950,8 +952,9 @@ void launch_gram_bf16(const __hip_bfloat16* X, float* G, int n, long d,
   }
 }
 
-void launch_gram_f32(const float* X, float* G, int n, long d,
-                     hipStream_t stream) {
+template <>
+void launch_gram<float>(const float* X, float* G, int n, long d,
+                        hipStream_t stream) {
   // the n>32 symmetric kernel's float4 loads need d % 4 == 0
   if (n <= 64 && d >= 64 && (n <= 32 || (d % 4) == 0)) {
     long kpw, blocks;

@@ -10,6 +10,7 @@
 // <=0.1 ms each — fixed overhead that caps multi-GPU scaling of the
 // d-sharded Krum (the (n,n) work is rank-replicated).
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 

@@ -1,0 +1,96 @@
+// Host launchers of the byzpy_amd gfx950 kernel library: the one place a
+// launcher signature is declared. Included by bind.cpp and by every .hip
+// file that defines one, so a signature drift fails to compile instead of
+// surfacing as an undefined symbol when _hip_ops.so is imported.
+//
+// Every launch_x<T> is defined for T in {float, __hip_bfloat16}, explicitly
+// instantiated next to its definition (INSTANTIATE_LAUNCHER, one block per
+// file). All launches enqueue on `stream`; none syncs the host.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <hip/hip_bf16.h>
+
+// Row cap of the kernels that stage per-row weights in LDS
+// (weiszfeld_update, cc_update, caf_colsum in rowops.hip). The bindings
+// reject larger n before launching; the kernels size their arrays by it.
+constexpr int MAX_N_LDS = 1024;
+
+// `template void f<T>(full signature)` without repeating the signature
+#define INSTANTIATE_LAUNCHER(f)           \
+  template decltype(f<float>) f<float>;   \
+  template decltype(f<__hip_bfloat16>) f<__hip_bfloat16>;
+
+// colsel.hip: register / LDS-sort column selection, n <= 512.
+// mode: 0 median, 1 trimmed mean, 2 mean-around-median
+template <typename T>
+void launch_colsel(const T* X, T* out, int n, long d, int mode, int f,
+                   hipStream_t stream);
+
+// rsel.hip: streaming radix-select engine for large n, same modes.
+// `state` is caller-zeroed d*4 u32 scratch; `med` is a d-float scratch,
+// read only by mode 2 (may be null otherwise)
+template <typename T>
+void launch_rsel(int mode, const T* X, T* out, unsigned int* state, float* med,
+                 int n, long d, int f, hipStream_t stream);
+
+// gram.hip
+template <typename T>
+void launch_gram(const T* X, float* G, int n, long d, hipStream_t stream);
+
+// rowops.hip
+template <typename T>
+void launch_row_sqnorms(const T* X, float* out, int n, long d,
+                        hipStream_t stream);
+template <typename T>
+void launch_row_center_sqdists(const T* X, const float* z, float* out, int n,
+                               long d, hipStream_t stream);
+template <typename T>
+void launch_row_scale(const T* X, const float* s, T* out, int n, long d,
+                      hipStream_t stream);
+template <typename T>
+void launch_mean_rows(const T* X, const int* idx, int k, T* out, long d,
+                      hipStream_t stream);
+template <typename T>
+void launch_group_mean_rows(const T* X, const int* idx, int g, int k, T* out,
+                            long d, hipStream_t stream);
+template <typename T>
+void launch_bucket_mean(const T* X, const int* perm, int n, int bucket, int nb,
+                        T* out, long d, hipStream_t stream);
+template <typename T>
+void launch_weiszfeld_update(const T* X, const float* z, const float* dist2,
+                             float* z_new, float* shift2, int n, long d,
+                             float eps, hipStream_t stream);
+template <typename T>
+void launch_grouped_weiszfeld(const T* X, const float* Z, float* dist2,
+                              float* Z_new, int G, int m, long d, float eps,
+                              hipStream_t stream);
+template <typename T>
+void launch_cc_update(const T* X, const float* v, const float* dist2,
+                      float* v_new, int n, long d, float c_tau, float eps,
+                      hipStream_t stream);
+template <typename T>
+void launch_caf_matvec(const T* X, const float* mu, const float* v, float* out,
+                       int n, long d, hipStream_t stream);
+template <typename T>
+void launch_caf_colsum(const T* X, const float* a, const float* mu,
+                       const float* scale, float* out, int n, long d,
+                       hipStream_t stream);
+
+// attacks.hip (K14)
+template <typename T>
+void launch_little(const T* X, T* out, int n, long d, float z,
+                   hipStream_t stream);
+template <typename T>
+void launch_gaussian_fill(T* out, long d, unsigned long long seed, float mu,
+                          float sigma, hipStream_t stream);
+
+// krumsel.hip / subsets.hip (K11): f32 Gram / distance matrices only
+void launch_krum_select(const float* G, int n, int f, int q, int* out_idx,
+                        float* out_scores, hipStream_t stream);
+void launch_smea_select(const float* G, const int* combos, int n, int m, int C,
+                        unsigned long long* best, hipStream_t stream);
+void launch_mda_pass1(const float* D2, const int* prefixes, int P, int n,
+                      int m, int npre, unsigned int* best, hipStream_t stream);
+void launch_mda_pass2(const float* D2, const int* prefixes, int P, int n,
+                      int m, int npre, unsigned int* best, int* subsets,
+                      int* found, hipStream_t stream);

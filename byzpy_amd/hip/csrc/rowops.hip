@@ -15,10 +15,12 @@
 // Column kernels: V consecutive coordinates per thread, row loop inside;
 // per-row weights (1/dist etc.) are staged once in LDS per block.
 #include "common.h"
+#include "launchers.h"
+#include <type_traits>
 
 namespace {
 
-constexpr int MAX_N_LDS = 1024;  // per-row weight stage (4 KB)
+// MAX_N_LDS (launchers.h): per-row weight stage, 4 KB
 
 // -- vector load/store ------------------------------------------------------
 
@@ -739,219 +741,165 @@ inline int slab_grid(long d, int n, int block) {
   return (int)(per_row < cap ? (per_row > 0 ? per_row : 1) : cap);
 }
 
-template <typename T>
-inline bool vec_ok(long d) {
-  return (d % VecTraits<T>::V) == 0;
+// Picks the VEC instantiation: calls fn(true_type) when d is a multiple of
+// the 16 B/lane vector width (VEC kernels), else fn(false_type) (scalar).
+template <typename T, typename F>
+inline void by_vec(long d, F&& fn) {
+  if ((d % VecTraits<T>::V) == 0)
+    fn(std::true_type{});
+  else
+    fn(std::false_type{});
 }
+
+// work items of a column kernel: V coordinates per thread when VEC
+template <typename T, bool VEC>
+inline long col_work(long d) {
+  return VEC ? d / VecTraits<T>::V : d;
+}
+
+constexpr int BLOCK = 256;  // threads per block, every launcher below
 
 }  // namespace
 
 // ---------------------------------------------------------------------------
-// host-side launchers
+// host-side launchers (declared in launchers.h)
 // ---------------------------------------------------------------------------
 
-#define FOR_TYPES(MACRO) MACRO(float) MACRO(__hip_bfloat16)
+#define VEC_OF(v) decltype(v)::value
 
 template <typename T>
 void launch_row_sqnorms(const T* X, float* out, int n, long d,
                         hipStream_t stream) {
-  const int block = 256;
-  dim3 grid(slab_grid(d, n, block), n);
-  if (vec_ok<T>(d))
-    hipLaunchKernelGGL((row_red_kernel<T, false, true>), grid, dim3(block), 0,
-                       stream, X, nullptr, out, d);
-  else
-    hipLaunchKernelGGL((row_red_kernel<T, false, false>), grid, dim3(block), 0,
-                       stream, X, nullptr, out, d);
+  dim3 grid(slab_grid(d, n, BLOCK), n);
+  by_vec<T>(d, [&](auto v) {
+    hipLaunchKernelGGL((row_red_kernel<T, false, VEC_OF(v)>), grid,
+                       dim3(BLOCK), 0, stream, X, nullptr, out, d);
+  });
 }
 
 template <typename T>
 void launch_row_center_sqdists(const T* X, const float* z, float* out, int n,
                                long d, hipStream_t stream) {
-  const int block = 256;
   const int groups = (n + DIST_GROUP - 1) / DIST_GROUP;
-  dim3 grid(slab_grid(d, groups, block), groups);
-  if (vec_ok<T>(d))
-    hipLaunchKernelGGL((center_sqdists_group_kernel<T, true>), grid,
-                       dim3(block), 0, stream, X, z, out, n, d);
-  else
-    hipLaunchKernelGGL((center_sqdists_group_kernel<T, false>), grid,
-                       dim3(block), 0, stream, X, z, out, n, d);
+  dim3 grid(slab_grid(d, groups, BLOCK), groups);
+  by_vec<T>(d, [&](auto v) {
+    hipLaunchKernelGGL((center_sqdists_group_kernel<T, VEC_OF(v)>), grid,
+                       dim3(BLOCK), 0, stream, X, z, out, n, d);
+  });
 }
 
 template <typename T>
 void launch_grouped_weiszfeld(const T* X, const float* Z, float* dist2,
                               float* Z_new, int G, int m, long d, float eps,
                               hipStream_t stream) {
-  const int block = 256;
-  dim3 grid(slab_grid(d, G, block), G);
-  if (vec_ok<T>(d)) {
-    hipLaunchKernelGGL((center_sqdists_grouped_kernel<T, true>), grid,
-                       dim3(block), 0, stream, X, Z, dist2, m, d);
-    hipLaunchKernelGGL((weiszfeld_update_grouped_kernel<T, true>), grid,
-                       dim3(block), 0, stream, X, Z, dist2, Z_new, m, d, eps);
-  } else {
-    hipLaunchKernelGGL((center_sqdists_grouped_kernel<T, false>), grid,
-                       dim3(block), 0, stream, X, Z, dist2, m, d);
-    hipLaunchKernelGGL((weiszfeld_update_grouped_kernel<T, false>), grid,
-                       dim3(block), 0, stream, X, Z, dist2, Z_new, m, d, eps);
-  }
+  dim3 grid(slab_grid(d, G, BLOCK), G);
+  by_vec<T>(d, [&](auto v) {
+    hipLaunchKernelGGL((center_sqdists_grouped_kernel<T, VEC_OF(v)>), grid,
+                       dim3(BLOCK), 0, stream, X, Z, dist2, m, d);
+    hipLaunchKernelGGL((weiszfeld_update_grouped_kernel<T, VEC_OF(v)>), grid,
+                       dim3(BLOCK), 0, stream, X, Z, dist2, Z_new, m, d, eps);
+  });
 }
-template void launch_grouped_weiszfeld<float>(const float*, const float*,
-                                              float*, float*, int, int, long,
-                                              float, hipStream_t);
-template void launch_grouped_weiszfeld<__hip_bfloat16>(
-    const __hip_bfloat16*, const float*, float*, float*, int, int, long,
-    float, hipStream_t);
 
 template <typename T>
 void launch_row_scale(const T* X, const float* s, T* out, int n, long d,
                       hipStream_t stream) {
-  const int block = 256;
-  dim3 grid(slab_grid(d, n, block), n);
-  if (vec_ok<T>(d))
-    hipLaunchKernelGGL((row_scale_kernel<T, true>), grid, dim3(block), 0,
+  dim3 grid(slab_grid(d, n, BLOCK), n);
+  by_vec<T>(d, [&](auto v) {
+    hipLaunchKernelGGL((row_scale_kernel<T, VEC_OF(v)>), grid, dim3(BLOCK), 0,
                        stream, X, s, out, d);
-  else
-    hipLaunchKernelGGL((row_scale_kernel<T, false>), grid, dim3(block), 0,
-                       stream, X, s, out, d);
+  });
 }
 
 template <typename T>
 void launch_mean_rows(const T* X, const int* idx, int k, T* out, long d,
                       hipStream_t stream) {
-  const int block = 256;
-  const bool v = vec_ok<T>(d);
-  const long work = v ? d / VecTraits<T>::V : d;
-  if (v)
-    hipLaunchKernelGGL((gather_mean_kernel<T, true, false>),
-                       dim3(col_grid(work, block)), dim3(block), 0, stream, X,
+  by_vec<T>(d, [&](auto v) {
+    const long work = col_work<T, VEC_OF(v)>(d);
+    hipLaunchKernelGGL((gather_mean_kernel<T, VEC_OF(v), false>),
+                       dim3(col_grid(work, BLOCK)), dim3(BLOCK), 0, stream, X,
                        idx, k, out, d);
-  else
-    hipLaunchKernelGGL((gather_mean_kernel<T, false, false>),
-                       dim3(col_grid(work, block)), dim3(block), 0, stream, X,
-                       idx, k, out, d);
+  });
 }
 
 template <typename T>
 void launch_group_mean_rows(const T* X, const int* idx, int g, int k, T* out,
                             long d, hipStream_t stream) {
-  const int block = 256;
-  const bool v = vec_ok<T>(d);
-  const long work = (v ? d / VecTraits<T>::V : d + 0) / (g > 4 ? 4 : 1) + 1;
-  dim3 grid(col_grid(work, block), g);
-  if (v)
-    hipLaunchKernelGGL((gather_mean_kernel<T, true, true>), grid, dim3(block),
-                       0, stream, X, idx, k, out, d);
-  else
-    hipLaunchKernelGGL((gather_mean_kernel<T, false, true>), grid, dim3(block),
-                       0, stream, X, idx, k, out, d);
+  by_vec<T>(d, [&](auto v) {
+    const long work = col_work<T, VEC_OF(v)>(d) / (g > 4 ? 4 : 1) + 1;
+    hipLaunchKernelGGL((gather_mean_kernel<T, VEC_OF(v), true>),
+                       dim3(col_grid(work, BLOCK), g), dim3(BLOCK), 0, stream,
+                       X, idx, k, out, d);
+  });
 }
 
 template <typename T>
 void launch_bucket_mean(const T* X, const int* perm, int n, int bucket, int nb,
                         T* out, long d, hipStream_t stream) {
-  const int block = 256;
-  const bool v = vec_ok<T>(d);
-  const long work = (v ? d / VecTraits<T>::V : d + 0) / (nb > 4 ? 4 : 1) + 1;
-  dim3 grid(col_grid(work, block), nb);
-  if (v)
-    hipLaunchKernelGGL((bucket_mean_kernel<T, true>), grid, dim3(block), 0,
-                       stream, X, perm, n, bucket, out, d);
-  else
-    hipLaunchKernelGGL((bucket_mean_kernel<T, false>), grid, dim3(block), 0,
-                       stream, X, perm, n, bucket, out, d);
+  by_vec<T>(d, [&](auto v) {
+    const long work = col_work<T, VEC_OF(v)>(d) / (nb > 4 ? 4 : 1) + 1;
+    hipLaunchKernelGGL((bucket_mean_kernel<T, VEC_OF(v)>),
+                       dim3(col_grid(work, BLOCK), nb), dim3(BLOCK), 0, stream,
+                       X, perm, n, bucket, out, d);
+  });
 }
 
 template <typename T>
 void launch_weiszfeld_update(const T* X, const float* z, const float* dist2,
                              float* z_new, float* shift2, int n, long d,
                              float eps, hipStream_t stream) {
-  const int block = 256;
-  const bool v = vec_ok<T>(d);
-  const long work = v ? d / VecTraits<T>::V : d;
-  if (v)
-    hipLaunchKernelGGL((weiszfeld_update_kernel<T, true>),
-                       dim3(col_grid(work, block)), dim3(block), 0, stream, X,
+  by_vec<T>(d, [&](auto v) {
+    const long work = col_work<T, VEC_OF(v)>(d);
+    hipLaunchKernelGGL((weiszfeld_update_kernel<T, VEC_OF(v)>),
+                       dim3(col_grid(work, BLOCK)), dim3(BLOCK), 0, stream, X,
                        z, dist2, z_new, shift2, n, d, eps);
-  else
-    hipLaunchKernelGGL((weiszfeld_update_kernel<T, false>),
-                       dim3(col_grid(work, block)), dim3(block), 0, stream, X,
-                       z, dist2, z_new, shift2, n, d, eps);
+  });
 }
 
 template <typename T>
 void launch_cc_update(const T* X, const float* v, const float* dist2,
                       float* v_new, int n, long d, float c_tau, float eps,
                       hipStream_t stream) {
-  const int block = 256;
-  const bool vo = vec_ok<T>(d);
-  const long work = vo ? d / VecTraits<T>::V : d;
-  if (vo)
-    hipLaunchKernelGGL((cc_update_kernel<T, true>),
-                       dim3(col_grid(work, block)), dim3(block), 0, stream, X,
+  by_vec<T>(d, [&](auto vec) {
+    const long work = col_work<T, VEC_OF(vec)>(d);
+    hipLaunchKernelGGL((cc_update_kernel<T, VEC_OF(vec)>),
+                       dim3(col_grid(work, BLOCK)), dim3(BLOCK), 0, stream, X,
                        v, dist2, v_new, n, d, c_tau, eps);
-  else
-    hipLaunchKernelGGL((cc_update_kernel<T, false>),
-                       dim3(col_grid(work, block)), dim3(block), 0, stream, X,
-                       v, dist2, v_new, n, d, c_tau, eps);
+  });
 }
 
 template <typename T>
 void launch_caf_matvec(const T* X, const float* mu, const float* v, float* out,
                        int n, long d, hipStream_t stream) {
-  const int block = 256;
   const int groups = (n + DIST_GROUP - 1) / DIST_GROUP;
-  dim3 grid(slab_grid(d, groups, block), groups);
-  if (vec_ok<T>(d))
-    hipLaunchKernelGGL((caf_matvec_group_kernel<T, true>), grid, dim3(block),
-                       0, stream, X, mu, v, out, n, d);
-  else
-    hipLaunchKernelGGL((caf_matvec_group_kernel<T, false>), grid, dim3(block),
-                       0, stream, X, mu, v, out, n, d);
+  dim3 grid(slab_grid(d, groups, BLOCK), groups);
+  by_vec<T>(d, [&](auto vec) {
+    hipLaunchKernelGGL((caf_matvec_group_kernel<T, VEC_OF(vec)>), grid,
+                       dim3(BLOCK), 0, stream, X, mu, v, out, n, d);
+  });
 }
 
 template <typename T>
 void launch_caf_colsum(const T* X, const float* a, const float* mu,
                        const float* scale, float* out, int n, long d,
                        hipStream_t stream) {
-  const int block = 256;
-  const bool vo = vec_ok<T>(d);
-  const long work = vo ? d / VecTraits<T>::V : d;
-  if (vo)
-    hipLaunchKernelGGL((caf_colsum_kernel<T, true>),
-                       dim3(col_grid(work, block)), dim3(block), 0, stream, X,
+  by_vec<T>(d, [&](auto v) {
+    const long work = col_work<T, VEC_OF(v)>(d);
+    hipLaunchKernelGGL((caf_colsum_kernel<T, VEC_OF(v)>),
+                       dim3(col_grid(work, BLOCK)), dim3(BLOCK), 0, stream, X,
                        a, mu, scale, out, n, d);
-  else
-    hipLaunchKernelGGL((caf_colsum_kernel<T, false>),
-                       dim3(col_grid(work, block)), dim3(block), 0, stream, X,
-                       a, mu, scale, out, n, d);
+  });
 }
+#undef VEC_OF
 
-// explicit instantiations for bind.cpp
-#define INSTANTIATE(T)                                                         \
-  template void launch_caf_matvec<T>(const T*, const float*, const float*,     \
-                                     float*, int, long, hipStream_t);          \
-  template void launch_caf_colsum<T>(const T*, const float*, const float*,     \
-                                     const float*, float*, int, long,          \
-                                     hipStream_t);                             \
-  template void launch_row_sqnorms<T>(const T*, float*, int, long,             \
-                                      hipStream_t);                            \
-  template void launch_row_center_sqdists<T>(const T*, const float*, float*,   \
-                                             int, long, hipStream_t);          \
-  template void launch_row_scale<T>(const T*, const float*, T*, int, long,     \
-                                    hipStream_t);                              \
-  template void launch_mean_rows<T>(const T*, const int*, int, T*, long,       \
-                                    hipStream_t);                              \
-  template void launch_group_mean_rows<T>(const T*, const int*, int, int, T*,  \
-                                          long, hipStream_t);                  \
-  template void launch_bucket_mean<T>(const T*, const int*, int, int, int, T*, \
-                                      long, hipStream_t);                      \
-  template void launch_weiszfeld_update<T>(const T*, const float*,             \
-                                           const float*, float*, float*, int,  \
-                                           long, float, hipStream_t);          \
-  template void launch_cc_update<T>(const T*, const float*, const float*,      \
-                                    float*, int, long, float, float,           \
-                                    hipStream_t);
-FOR_TYPES(INSTANTIATE)
-#undef INSTANTIATE
+INSTANTIATE_LAUNCHER(launch_row_sqnorms)
+INSTANTIATE_LAUNCHER(launch_row_center_sqdists)
+INSTANTIATE_LAUNCHER(launch_grouped_weiszfeld)
+INSTANTIATE_LAUNCHER(launch_row_scale)
+INSTANTIATE_LAUNCHER(launch_mean_rows)
+INSTANTIATE_LAUNCHER(launch_group_mean_rows)
+INSTANTIATE_LAUNCHER(launch_bucket_mean)
+INSTANTIATE_LAUNCHER(launch_weiszfeld_update)
+INSTANTIATE_LAUNCHER(launch_cc_update)
+INSTANTIATE_LAUNCHER(launch_caf_matvec)
+INSTANTIATE_LAUNCHER(launch_caf_colsum)

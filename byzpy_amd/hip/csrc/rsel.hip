@@ -2,9 +2,8 @@
 // statistics (SURVEY.md K1-K3 at n > ~192, where the in-LDS sort
 // re-touches every element log^2 P times and collapses to ~0.1-0.6 TB/s).
 //
-// The specialized 2-pass bf16 MEDIAN kernels live in colsel.hip
-// (rsel_pass1/2). This file generalizes the idea to every other
-// mode x dtype combination as a sequence of STREAMING passes, each
+// Every large-n mode x dtype combination (MEDIAN, TRIMMED, MEAMED x
+// f32, bf16) runs on this engine as a sequence of STREAMING passes, each
 // HBM-bound and coalesced the same way (64 adjacent columns per block,
 // 4 row slices per column):
 //
@@ -31,7 +30,8 @@
 //   [2] prefix for rank 1   [3] count below prefix1
 // Ranks are 1-based. Counts are exact after the last level.
 #include "common.h"
-#include <cstdlib>
+#include "launchers.h"
+#include <type_traits>
 
 namespace {
 
@@ -427,61 +427,14 @@ void run_levels(const T* X, const float* med, u32* state, int n, long d,
 }  // namespace
 
 // ---------------------------------------------------------------------------
-// host-side drivers (called from bind.cpp; all launches enqueue on
+// host-side driver (called from bind.cpp; all launches enqueue on
 // `stream`, no host syncs). `state` is caller-zeroed d*4 u32 scratch;
 // `med` is a d-float scratch for MEAMED.
 // ---------------------------------------------------------------------------
 
-void launch_rsel_trimmed_bf16(const __hip_bfloat16* X, __hip_bfloat16* out,
-                              unsigned int* state, int n, long d, int f,
-                              hipStream_t stream) {
-  run_levels<__hip_bfloat16, VAL_BF16, true>(X, nullptr, state, n, d,
-                                             (u32)(f + 1), (u32)(n - f),
-                                             stream);
-  const long grid = (d + RS_COLS - 1) / RS_COLS;
-  hipLaunchKernelGGL((rsel_trimmed_sum_kernel<__hip_bfloat16, VAL_BF16>),
-                     dim3((unsigned)grid), dim3(RS_THREADS), 0, stream, X,
-                     state, out, n, d, f);
-}
-
-void launch_rsel_trimmed_f32(const float* X, float* out, unsigned int* state,
-                             int n, long d, int f, hipStream_t stream) {
-  run_levels<float, VAL_F32, true>(X, nullptr, state, n, d, (u32)(f + 1),
-                                   (u32)(n - f), stream);
-  const long grid = (d + RS_COLS - 1) / RS_COLS;
-  hipLaunchKernelGGL((rsel_trimmed_sum_kernel<float, VAL_F32>),
-                     dim3((unsigned)grid), dim3(RS_THREADS), 0, stream, X,
-                     state, out, n, d, f);
-}
-
-void launch_rsel_median_bf16(const __hip_bfloat16* X, __hip_bfloat16* out,
-                             unsigned int* state, int n, long d,
-                             hipStream_t stream) {
-  const u32 t_lo = (u32)((n - 1) >> 1) + 1, t_hi = (u32)(n >> 1) + 1;
-  run_levels<__hip_bfloat16, VAL_BF16, true>(X, nullptr, state, n, d, t_lo,
-                                             t_hi, stream);
-  const long grid = (d + 255) / 256;
-  hipLaunchKernelGGL((rsel_median_out_kernel<__hip_bfloat16, VAL_BF16, false>),
-                     dim3((unsigned)grid), dim3(256), 0, stream, state, out,
-                     d);
-}
-
-void launch_rsel_median_f32(const float* X, float* out, unsigned int* state,
-                            int n, long d, hipStream_t stream) {
-  const u32 t_lo = (u32)((n - 1) >> 1) + 1, t_hi = (u32)(n >> 1) + 1;
-  run_levels<float, VAL_F32, true>(X, nullptr, state, n, d, t_lo, t_hi,
-                                   stream);
-  const long elems = d;
-  const long grid = (elems + 255) / 256;
-  hipLaunchKernelGGL((rsel_median_out_kernel<float, VAL_F32, false>),
-                     dim3((unsigned)grid), dim3(256), 0, stream, state, out,
-                     d);
-}
-
 // MEAMED: median levels -> med buffer -> dev-key rank (n-f) -> sum pass.
-// Caller re-zeroes `state` between the two selections? No — the dev
-// selection reuses slot 0/1 only, and must start from prefix 0: the
-// med_out kernel is followed by a device-side state reset here.
+// The dev selection reuses state slots 0/1 only and must start from
+// prefix 0, so the med_out kernel is followed by a device-side reset.
 namespace {
 __global__ void rsel_state_reset_kernel(u32* __restrict__ state, long d) {
   const long col = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -492,33 +445,35 @@ __global__ void rsel_state_reset_kernel(u32* __restrict__ state, long d) {
 }
 }  // namespace
 
-template <typename T, int KK>
-static void rsel_meamed_impl(const T* X, T* out, unsigned int* state,
-                             float* med, int n, long d, int f,
-                             hipStream_t stream) {
+template <typename T>
+void launch_rsel(int mode, const T* X, T* out, unsigned int* state, float* med,
+                 int n, long d, int f, hipStream_t stream) {
+  constexpr int KK = std::is_same<T, float>::value ? VAL_F32 : VAL_BF16;
+  const long grid = (d + RS_COLS - 1) / RS_COLS;  // 64-column blocks
+  const long egrid = (d + 255) / 256;             // one thread per column
+  if (mode == 1) {  // TRIMMED: ranks f+1 and n-f bound the kept range
+    run_levels<T, KK, true>(X, nullptr, state, n, d, (u32)(f + 1),
+                            (u32)(n - f), stream);
+    hipLaunchKernelGGL((rsel_trimmed_sum_kernel<T, KK>), dim3((unsigned)grid),
+                       dim3(RS_THREADS), 0, stream, X, state, out, n, d, f);
+    return;
+  }
   const u32 t_lo = (u32)((n - 1) >> 1) + 1, t_hi = (u32)(n >> 1) + 1;
   run_levels<T, KK, true>(X, nullptr, state, n, d, t_lo, t_hi, stream);
-  const long egrid = (d + 255) / 256;
+  if (mode == 0) {  // MEDIAN
+    hipLaunchKernelGGL((rsel_median_out_kernel<T, KK, false>),
+                       dim3((unsigned)egrid), dim3(256), 0, stream, state, out,
+                       d);
+    return;
+  }
   hipLaunchKernelGGL((rsel_median_out_kernel<T, KK, true>),
                      dim3((unsigned)egrid), dim3(256), 0, stream, state, med,
                      d);
   hipLaunchKernelGGL(rsel_state_reset_kernel, dim3((unsigned)egrid), dim3(256),
                      0, stream, state, d);
   run_levels<T, DEV_KEY, false>(X, med, state, n, d, (u32)(n - f), 0, stream);
-  const long grid = (d + RS_COLS - 1) / RS_COLS;
   hipLaunchKernelGGL((rsel_meamed_sum_kernel<T, KK>), dim3((unsigned)grid),
                      dim3(RS_THREADS), 0, stream, X, med, state, out, n, d, f);
 }
 
-void launch_rsel_meamed_bf16(const __hip_bfloat16* X, __hip_bfloat16* out,
-                             unsigned int* state, float* med, int n, long d,
-                             int f, hipStream_t stream) {
-  rsel_meamed_impl<__hip_bfloat16, VAL_BF16>(X, out, state, med, n, d, f,
-                                             stream);
-}
-
-void launch_rsel_meamed_f32(const float* X, float* out, unsigned int* state,
-                            float* med, int n, long d, int f,
-                            hipStream_t stream) {
-  rsel_meamed_impl<float, VAL_F32>(X, out, state, med, n, d, f, stream);
-}
+INSTANTIATE_LAUNCHER(launch_rsel)

@@ -16,8 +16,9 @@
 // remaining candidates with per-level incremental max-distance arrays in
 // LDS, sharing the global best diameter through an atomicMin every
 // improvement. A second bounded pass recovers the lexicographically
-// smallest optimal subset (host parity: bind.cpp mda_search's dfs2).
+// smallest optimal subset (host parity: mda_host.cpp mda_search's dfs2).
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 
@@ -144,7 +145,7 @@ smea_select_kernel(const float* __restrict__ G, const int* __restrict__ combos,
 // PASS 2 (FIND=true): bounded lex-order DFS; the FIRST completion is the
 // prefix's lex-smallest subset with diameter <= bound. The dispatcher
 // picks the first found prefix in lex order = the globally lex-smallest
-// optimal subset (host parity: bind.cpp mda_search's dfs2).
+// optimal subset (host parity: mda_host.cpp mda_search's dfs2).
 template <bool FIND>
 __global__ void __launch_bounds__(64)
 mda_dfs_kernel(const float* __restrict__ D2g, const int* __restrict__ prefixes,

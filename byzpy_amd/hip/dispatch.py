@@ -72,54 +72,69 @@ def median_and_gram(X: torch.Tensor):
     return median(X), gram(X)
 
 
+# Gram -> squared distances -> Krum scores -> winners. Device-agnostic
+# torch on the tiny (n, n) Gram, written ONCE: cross-rank Krum winner-set
+# consistency rests on every rank and every engine (direct, chunked pool,
+# d-sharded) evaluating exactly these expressions. ops/functional.py keeps
+# its own independent text as the oracle.
+
+
+def sq_dists_from_gram(G: torch.Tensor) -> torch.Tensor:
+    """||a||^2 + ||b||^2 - 2 a.b clamped at 0, from an (n, n) Gram or a
+    batch (B, n, n) of them."""
+    norms = torch.diagonal(G, dim1=-2, dim2=-1)
+    return (norms[..., :, None] + norms[..., None, :] - 2.0 * G).clamp_(min=0.0)
+
+
+def krum_scores_from_gram(G: torch.Tensor, f: int) -> torch.Tensor:
+    """score_i = sum of the n-f-1 smallest squared distances from row i to
+    the others (the self-distance is masked with +inf)."""
+    n = G.shape[0]
+    D2 = sq_dists_from_gram(G)
+    D2 = D2 + torch.diag(
+        torch.full((n,), float("inf"), device=G.device, dtype=G.dtype)
+    )
+    return torch.topk(D2, k=n - f - 1, dim=1, largest=False).values.sum(dim=1)
+
+
+def krum_winners_from_gram(G: torch.Tensor, f: int, q: int) -> torch.Tensor:
+    """int32 indices of the q best-scored rows: the fused krum_select
+    kernel on device up to its n = 512 cap, else topk over the scores."""
+    if _gpu(G) and G.shape[0] <= 512:
+        return _hip.require().krum_select(G, int(f), int(q))
+    scores = krum_scores_from_gram(G, f)
+    return torch.topk(scores, k=q, largest=False).indices.to(torch.int32)
+
+
+def nearest_rows_from_gram(G: torch.Tensor, k: int) -> torch.Tensor:
+    """Per row, the indices of its k nearest rows (itself included)."""
+    return torch.topk(sq_dists_from_gram(G), k=k, dim=-1, largest=False).indices
+
+
 def pairwise_sq_dists(X: torch.Tensor) -> torch.Tensor:
     if _gpu(X):
-        G = gram(X)
-        norms = torch.diagonal(G)
-        D2 = norms[:, None] + norms[None, :] - 2.0 * G
-        return D2.clamp_(min=0.0)
+        return sq_dists_from_gram(gram(X))
     return F.pairwise_sq_dists(X)
 
 
 def multi_krum_scores(X: torch.Tensor, f: int) -> torch.Tensor:
     n = X.shape[0]
-    k = n - f - 1
-    if k < 1:
+    if n - f - 1 < 1:
         raise ValueError(f"need n - f - 1 >= 1, got n={n}, f={f}")
     if _gpu(X):
-        D2 = pairwise_sq_dists(X)
-        D2 = D2 + torch.diag(
-            torch.full((n,), float("inf"), device=X.device, dtype=D2.dtype)
-        )
-        smallest = torch.topk(D2, k=k, dim=1, largest=False).values
-        return smallest.sum(dim=1)
+        return krum_scores_from_gram(gram(X), f)
     return F.multi_krum_scores(X, f)
 
 
 def multi_krum(X: torch.Tensor, f: int, q: int) -> torch.Tensor:
     if _gpu(X):
-        n = X.shape[0]
-        G = gram(X)
-        if n <= 512:
-            idx = _hip.require().krum_select(G, int(f), int(q))
-        else:
-            scores = _scores_from_gram(G, n, f)
-            idx = torch.topk(scores, k=q, largest=False).indices.to(torch.int32)
-        return mean_rows(X, idx)
+        return mean_rows(X, krum_winners_from_gram(gram(X), f, q))
     return F.multi_krum(X, f, q)
-
-
-def _scores_from_gram(G: torch.Tensor, n: int, f: int) -> torch.Tensor:
-    norms = torch.diagonal(G)
-    D2 = (norms[:, None] + norms[None, :] - 2.0 * G).clamp_(min=0.0)
-    D2 = D2 + torch.diag(torch.full((n,), float("inf"), device=G.device, dtype=D2.dtype))
-    return torch.topk(D2, k=n - f - 1, dim=1, largest=False).values.sum(dim=1)
 
 
 def krum(X: torch.Tensor, f: int) -> torch.Tensor:
     if _gpu(X) and X.shape[0] <= 512:
-        G = gram(X)
-        idx = _hip.require().krum_select(G, int(f), 1)
+        idx = krum_winners_from_gram(gram(X), f, 1)
         return X[idx.long()[0]].clone()
     scores = multi_krum_scores(X, f)
     return X[int(torch.argmin(scores))].clone()
@@ -130,6 +145,13 @@ def mean_rows(X: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     if _gpu(X):
         return _hip.require().mean_rows(X.contiguous(), idx.to(torch.int32))
     return X.float()[idx].mean(dim=0).to(X.dtype)
+
+
+def group_mean_rows(X: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """Row g of the result is the mean of rows idx[g] (K10, NNM mixing)."""
+    if _gpu(X):
+        return _hip.require().group_mean_rows(X.contiguous(), idx.to(torch.int32))
+    return X.float()[idx.long()].mean(dim=1).to(X.dtype)
 
 
 # -- row norms / scaling (K8, K12) ------------------------------------------
@@ -323,9 +345,7 @@ def nnm_grouped(X3: torch.Tensor, f: int) -> torch.Tensor:
     else:
         Xf = X3.float()
         Gm = torch.bmm(Xf, Xf.transpose(1, 2))
-    norms = torch.diagonal(Gm, dim1=1, dim2=2)
-    D2 = (norms[:, :, None] + norms[:, None, :] - 2.0 * Gm).clamp_(min=0.0)
-    idx = torch.topk(D2, k=k, dim=2, largest=False).indices
+    idx = nearest_rows_from_gram(Gm, k)
     mask = torch.zeros_like(Gm)
     mask.scatter_(2, idx, 1.0 / k)
     return torch.bmm(mask.to(X3.dtype), X3)
@@ -372,12 +392,9 @@ def bucketing(
 
 
 def nnm(X: torch.Tensor, f: int) -> torch.Tensor:
-    n = X.shape[0]
-    k = n - f
     if _gpu(X):
-        D2 = pairwise_sq_dists(X)
-        idx = torch.topk(D2, k=k, dim=1, largest=False).indices.to(torch.int32)
-        return _hip.require().group_mean_rows(X.contiguous(), idx)
+        idx = nearest_rows_from_gram(gram(X), X.shape[0] - f)
+        return group_mean_rows(X, idx)
     return F.nnm(X, f)
 
 

@@ -17,6 +17,7 @@ from typing import Sequence
 import torch
 
 from byzpy_amd.hip import dispatch as D
+from byzpy_amd.hip import require
 from byzpy_amd.ops import functional as F
 from byzpy_amd.parallel.dist import all_reduce_
 
@@ -49,63 +50,25 @@ def median_and_multi_krum(X_local: torch.Tensor, f: int, q: int):
     then one (n, n) all-reduce yields a Krum selection identical on
     every rank (RCCL all-reduce returns bitwise-identical sums on all
     ranks, so the winner set never diverges)."""
-    from byzpy_amd.hip import dispatch as _D
-
-    n = X_local.shape[0]
-    med, G = _D.median_and_gram(X_local)
-    G = all_reduce_(G)
-    if X_local.is_cuda and n <= 512:
-        from byzpy_amd import hip as _h
-
-        winners = _h.require().krum_select(G, int(f), int(q))
-        return med, D.mean_rows(X_local, winners)
-    norms = torch.diagonal(G)
-    D2 = (norms[:, None] + norms[None, :] - 2.0 * G).clamp_(min=0.0)
-    D2 = D2 + torch.diag(torch.full((n,), float("inf"), device=X_local.device))
-    k = n - f - 1
-    scores = torch.topk(D2, k=k, dim=1, largest=False).values.sum(dim=1)
-    winners = torch.topk(scores, k=q, largest=False).indices
-    return med, D.mean_rows(X_local, winners.to(torch.int32))
+    med, G = D.median_and_gram(X_local)
+    winners = D.krum_winners_from_gram(all_reduce_(G), f, q)
+    return med, D.mean_rows(X_local, winners)
 
 
 def multi_krum(X_local: torch.Tensor, f: int, q: int) -> torch.Tensor:
-    n = X_local.shape[0]
-    G = _global_gram(X_local)
-    if X_local.is_cuda and n <= 512:
-        from byzpy_amd.hip import require
-
-        winners = require().krum_select(G, int(f), int(q))
-        return D.mean_rows(X_local, winners)
-    norms = torch.diagonal(G)
-    D2 = (norms[:, None] + norms[None, :] - 2.0 * G).clamp_(min=0.0)
-    D2 = D2 + torch.diag(torch.full((n,), float("inf"), device=X_local.device))
-    k = n - f - 1
-    scores = torch.topk(D2, k=k, dim=1, largest=False).values.sum(dim=1)
-    winners = torch.topk(scores, k=q, largest=False).indices
-    return D.mean_rows(X_local, winners.to(torch.int32))
+    winners = D.krum_winners_from_gram(_global_gram(X_local), f, q)
+    return D.mean_rows(X_local, winners)
 
 
 def krum(X_local: torch.Tensor, f: int) -> torch.Tensor:
-    n = X_local.shape[0]
-    G = _global_gram(X_local)
-    norms = torch.diagonal(G)
-    D2 = (norms[:, None] + norms[None, :] - 2.0 * G).clamp_(min=0.0)
-    D2 = D2 + torch.diag(torch.full((n,), float("inf"), device=X_local.device))
-    scores = torch.topk(D2, k=n - f - 1, dim=1, largest=False).values.sum(dim=1)
+    scores = D.krum_scores_from_gram(_global_gram(X_local), f)
     return X_local[int(torch.argmin(scores))].clone()
 
 
 def nnm(X_local: torch.Tensor, f: int) -> torch.Tensor:
-    n = X_local.shape[0]
     G = _global_gram(X_local)
-    norms = torch.diagonal(G)
-    D2 = (norms[:, None] + norms[None, :] - 2.0 * G).clamp_(min=0.0)
-    idx = torch.topk(D2, k=n - f, dim=1, largest=False).indices.to(torch.int32)
-    if X_local.is_cuda:
-        from byzpy_amd.hip import require
-
-        return require().group_mean_rows(X_local.contiguous(), idx)
-    return X_local.float()[idx.long()].mean(dim=1).to(X_local.dtype)
+    idx = D.nearest_rows_from_gram(G, X_local.shape[0] - f)
+    return D.group_mean_rows(X_local, idx)
 
 
 # -- norm-wise: (n,) all-reduce ---------------------------------------------
@@ -147,6 +110,16 @@ def bucketing(
 
 # -- iterative fixed-point: per-iteration (n,) all-reduce -------------------
 
+# The fused update kernels stage one weight per row in LDS and the bindings
+# reject n above this cap; larger n runs the torch formulas on the device
+# (same routing as hip/dispatch.py).
+_LDS_MAX_ROWS = 1024
+
+
+def _fused_rows_ok(X_local: torch.Tensor) -> bool:
+    return X_local.is_cuda and X_local.shape[0] <= _LDS_MAX_ROWS
+
+
 def geometric_median(
     X_local: torch.Tensor,
     *,
@@ -160,13 +133,11 @@ def geometric_median(
     convergence polls — drops the per-poll shift all-reduce AND the host
     sync, leaving one (n,) all-reduce per iteration (the minimum for the
     d-sharded layout)."""
-    if not X_local.is_cuda:
-        return _geometric_median_cpu(
+    if not _fused_rows_ok(X_local):
+        return _geometric_median_torch(
             X_local, tol=tol, max_iter=max_iter, eps=eps, init=init,
             fixed_iters=fixed_iters,
         )
-    from byzpy_amd.hip import require
-
     ext = require()
     Xc = X_local.contiguous()
     z = (D.median(Xc) if init == "median" else Xc.float().mean(dim=0)).float()
@@ -189,7 +160,9 @@ def geometric_median(
     return z.to(X_local.dtype)
 
 
-def _geometric_median_cpu(X, *, tol, max_iter, eps, init, fixed_iters=None):
+def _geometric_median_torch(X, *, tol, max_iter, eps, init, fixed_iters=None):
+    """Device-agnostic torch Weiszfeld: CPU shards, and device shards with
+    more rows than the fused kernel's LDS stage holds."""
     Xf = X.float()
     z = (F.median(Xf) if init == "median" else Xf.mean(dim=0)).float()
     iters = int(fixed_iters) if fixed_iters is not None else max_iter
@@ -216,23 +189,8 @@ def centered_clipping(
     eps: float = 1e-12,
     init: str = "mean",
 ) -> torch.Tensor:
-    n = X_local.shape[0]
-    if not X_local.is_cuda:
-        Xf = X_local.float()
-        if init == "mean":
-            v = Xf.mean(dim=0)
-        elif init == "median":
-            v = F.median(Xf).float()
-        else:
-            v = torch.zeros_like(Xf[0])
-        for _ in range(M):
-            dist2 = all_reduce_(((Xf - v[None, :]) ** 2).sum(dim=1))
-            norms = dist2.sqrt().clamp_(min=eps)
-            alpha = torch.clamp(c_tau / norms, max=1.0)
-            v = v + (alpha[:, None] * (Xf - v[None, :])).sum(dim=0) / n
-        return v.to(X_local.dtype)
-    from byzpy_amd.hip import require
-
+    if not _fused_rows_ok(X_local):
+        return _centered_clipping_torch(X_local, c_tau, M, eps, init)
     ext = require()
     Xc = X_local.contiguous()
     if init == "mean":
@@ -245,3 +203,21 @@ def centered_clipping(
         dist2 = all_reduce_(ext.row_center_sqdists(Xc, v))
         v = ext.cc_apply(Xc, v, dist2, float(c_tau), float(eps))
     return v.to(X_local.dtype)
+
+
+def _centered_clipping_torch(X, c_tau, M, eps, init):
+    """Device-agnostic torch form (see _geometric_median_torch)."""
+    n = X.shape[0]
+    Xf = X.float()
+    if init == "mean":
+        v = Xf.mean(dim=0)
+    elif init == "median":
+        v = F.median(Xf).float()
+    else:
+        v = torch.zeros_like(Xf[0])
+    for _ in range(M):
+        dist2 = all_reduce_(((Xf - v[None, :]) ** 2).sum(dim=1))
+        norms = dist2.sqrt().clamp_(min=eps)
+        alpha = torch.clamp(c_tau / norms, max=1.0)
+        v = v + (alpha[:, None] * (Xf - v[None, :])).sum(dim=0) / n
+    return v.to(X.dtype)

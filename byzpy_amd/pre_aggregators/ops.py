@@ -146,12 +146,8 @@ class NearestNeighborMixing(PreAggregator):
     def reduce_subtasks(self, ctx: OpContext, results: List[Any], **inputs: Any) -> Any:
         ref, X, like, handles = ctx.metadata.pop("_op_pending")
         try:
-            G = sum(results)
-            norms = torch.diagonal(G)
-            D2 = (norms[:, None] + norms[None, :] - 2.0 * G).clamp_(min=0.0)
-            k = X.shape[0] - self.f
-            idx = torch.topk(D2, k=k, dim=1, largest=False).indices
-            out = X.float()[idx].mean(dim=1).to(X.dtype)
+            idx = D.nearest_rows_from_gram(sum(results), X.shape[0] - self.f)
+            out = D.group_mean_rows(X, idx)
             return [to_like(row, like) for row in out]
         finally:
             self._cleanup(handles)

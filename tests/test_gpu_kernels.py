@@ -945,3 +945,199 @@ class TestDeterminism:
             assert torch.allclose(
                 a.float(), b.float(), atol=tol * scale, rtol=1e-5
             ), f"{name} drifted beyond ulp scale"
+
+
+# -- binding layer: dtype / vector-width selection and the LDS row cap -------
+# Every _hip_ops binding that takes an (n, d) matrix, called directly at
+# n = 5 in both dtypes: d = 33 is no multiple of either vector width (4 f32
+# / 8 bf16 lanes -> scalar kernels, and odd d keeps bf16 colsel off the
+# packed path); d = 64 takes the vector kernels. References run on the CPU
+# copy of the (dtype-rounded) input.
+
+_SMALL_N = 5
+_SMALL_SEED = 22  # no exact |x - med| ties at the MEAMED window boundary
+
+
+def _wz_step(Xf, z, eps=1e-12):
+    w = 1.0 / (Xf - z[None, :]).norm(dim=1).clamp_(min=eps)
+    return (w[:, None] * Xf).sum(dim=0) / w.sum()
+
+
+def _cc_step(Xf, v, c_tau, eps=1e-12):
+    diff = Xf - v[None, :]
+    alpha = torch.clamp(c_tau / diff.norm(dim=1).clamp_(min=eps), max=1.0)
+    return v + (alpha[:, None] * diff).sum(dim=0) / Xf.shape[0]
+
+
+def _small_cases():
+    """name -> (binding call on device inputs, reference on CPU inputs).
+    Each takes (ext, X, aux) / (Xf, aux); aux holds the shared f32 vectors."""
+    idx = [3, 0, 4]
+    gidx = [[0, 1, 2], [4, 4, 1]]
+    perm = [2, 0, 4, 1, 3]
+
+    def dev_i32(v, like):
+        return torch.tensor(v, dtype=torch.int32, device=like.device)
+
+    def shift(like):
+        return torch.zeros((), device=like.device)
+
+    return {
+        "colsel_median": (
+            lambda e, X, a: e.colsel(X, 0, 0), lambda Xf, a: F.median(Xf)),
+        "colsel_trimmed": (
+            lambda e, X, a: e.colsel(X, 1, 1), lambda Xf, a: F.trimmed_mean(Xf, 1)),
+        "colsel_meamed": (
+            lambda e, X, a: e.colsel(X, 2, 1),
+            lambda Xf, a: F.mean_of_medians(Xf, 1)),
+        "row_sqnorms": (
+            lambda e, X, a: e.row_sqnorms(X), lambda Xf, a: (Xf * Xf).sum(dim=1)),
+        "row_center_sqdists": (
+            lambda e, X, a: e.row_center_sqdists(X, a["z"]),
+            lambda Xf, a: ((Xf - a["z"][None, :]) ** 2).sum(dim=1)),
+        "row_scale": (
+            lambda e, X, a: e.row_scale(X, a["s"]),
+            lambda Xf, a: Xf * a["s"][:, None]),
+        "mean_rows": (
+            lambda e, X, a: e.mean_rows(X, dev_i32(idx, X)),
+            lambda Xf, a: Xf[idx].mean(dim=0)),
+        "group_mean_rows": (
+            lambda e, X, a: e.group_mean_rows(X, dev_i32(gidx, X)),
+            lambda Xf, a: Xf[torch.tensor(gidx)].mean(dim=1)),
+        "bucket_mean": (
+            lambda e, X, a: e.bucket_mean(X, dev_i32(perm, X), 2),
+            lambda Xf, a: F.bucketing(Xf, 2, perm)),
+        "gram": (lambda e, X, a: e.gram(X), lambda Xf, a: Xf @ Xf.T),
+        "weiszfeld_iter": (
+            lambda e, X, a: e.weiszfeld_iter(X, a["z"], 1e-12, shift(X)),
+            lambda Xf, a: _wz_step(Xf, a["z"])),
+        "weiszfeld_apply": (
+            lambda e, X, a: e.weiszfeld_apply(
+                X, a["z"], e.row_center_sqdists(X, a["z"]), 1e-12, shift(X)),
+            lambda Xf, a: _wz_step(Xf, a["z"])),
+        "cc_iter": (
+            lambda e, X, a: e.cc_iter(X, a["z"], 0.7, 1e-12),
+            lambda Xf, a: _cc_step(Xf, a["z"], 0.7)),
+        "cc_apply": (
+            lambda e, X, a: e.cc_apply(
+                X, a["z"], e.row_center_sqdists(X, a["z"]), 0.7, 1e-12),
+            lambda Xf, a: _cc_step(Xf, a["z"], 0.7)),
+        "caf_matvec": (
+            lambda e, X, a: e.caf_matvec(X, a["z"], a["v"]),
+            lambda Xf, a: (Xf - a["z"][None, :]) @ a["v"]),
+        "caf_colsum": (
+            lambda e, X, a: e.caf_colsum(X, a["s"], a["z"], a["scale"]),
+            lambda Xf, a: a["scale"]
+            * (a["s"][:, None] * (Xf - a["z"][None, :])).sum(dim=0)),
+        "caf_colsum_plain": (
+            lambda e, X, a: e.caf_colsum(X, a["s"]),
+            lambda Xf, a: (a["s"][:, None] * Xf).sum(dim=0)),
+        "little_fused": (
+            lambda e, X, a: e.little_fused(X, 1.5),
+            lambda Xf, a: Xf.mean(dim=0) + 1.5 * Xf.std(dim=0, unbiased=False)),
+    }
+
+
+_SMALL_CASES = _small_cases()
+
+
+@pytest.fixture(scope="module")
+def small_inputs():
+    """(d, dtype) -> (X on device, X.float() on CPU, aux on device, aux on
+    CPU); built once, never modified."""
+    out = {}
+    for d in (33, 64):
+        g = torch.Generator().manual_seed(_SMALL_SEED + d)
+        aux = {
+            "z": torch.randn(d, generator=g),
+            "v": torch.randn(d, generator=g),
+            "s": torch.rand(_SMALL_N, generator=g) + 0.5,
+            "scale": torch.tensor(0.25),
+        }
+        aux_dev = {k: v.cuda() for k, v in aux.items()}
+        for dtype in DTYPES:
+            X = _rand(_SMALL_N, d, dtype, seed=_SMALL_SEED)
+            out[d, dtype] = (X, X.float().cpu(), aux_dev, aux)
+    return out
+
+
+@pytest.mark.parametrize("d", [33, 64])
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("op", sorted(_SMALL_CASES))
+def test_binding_small_n_both_dtypes_both_widths(small_inputs, op, dtype, d):
+    from byzpy_amd.hip import require
+
+    X, Xf, aux_dev, aux = small_inputs[d, dtype]
+    if op == "colsel_meamed":  # precondition: the kept window is unambiguous
+        dev = (Xf - F.median(Xf)[None, :]).abs().sort(dim=0).values
+        assert (dev[_SMALL_N - 1] > dev[_SMALL_N - 2]).all()
+    run, ref = _SMALL_CASES[op]
+    out = run(require(), X, aux_dev)
+    expect = ref(Xf, aux)
+    assert out.shape == expect.shape
+    assert torch.allclose(out.float().cpu(), expect, **_tol(dtype)), (
+        f"{op} d={d} {dtype}: max err "
+        f"{(out.float().cpu() - expect).abs().max().item():.3e}"
+    )
+
+
+@pytest.mark.parametrize("d", [33, 64])
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_binding_grouped_weiszfeld_small(dtype, d):
+    from byzpy_amd.hip import require
+
+    g = torch.Generator().manual_seed(_SMALL_SEED)
+    X3 = torch.randn(2, 3, d, generator=g).to("cuda", dtype)
+    Z = torch.randn(2, d, generator=g)
+    out = require().weiszfeld_iter_grouped(X3, Z.cuda(), 1e-12)
+    X3f = X3.float().cpu()
+    expect = torch.stack([_wz_step(X3f[i], Z[i]) for i in range(2)])
+    assert torch.allclose(out.cpu(), expect, **_tol(dtype))
+
+
+def test_lds_row_cap_rejected_by_every_lds_staging_binding():
+    """weiszfeld_update / cc_update / caf_colsum stage one weight per row in
+    a 1024-float LDS array: all five bindings that launch them must refuse
+    n = 1025 (by name) instead of writing past it."""
+    from byzpy_amd.hip import require
+
+    ext = require()
+    n, d = 1025, 8
+    X = _rand(n, d)
+    z = torch.zeros(d, device="cuda")
+    dist2 = torch.ones(n, device="cuda")
+    a = torch.ones(n, device="cuda")
+    shift = torch.zeros((), device="cuda")
+    calls = {
+        "weiszfeld_iter": lambda: ext.weiszfeld_iter(X, z, 1e-12, shift),
+        "weiszfeld_apply": lambda: ext.weiszfeld_apply(X, z, dist2, 1e-12, shift),
+        "cc_iter": lambda: ext.cc_iter(X, z, 0.7, 1e-12),
+        "cc_apply": lambda: ext.cc_apply(X, z, dist2, 0.7, 1e-12),
+        "caf_colsum": lambda: ext.caf_colsum(X, a),
+    }
+    for op, call in calls.items():
+        with pytest.raises(RuntimeError, match=rf"\b{op} supports n <= 1024"):
+            call()
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_sharded_iterative_ops_above_lds_row_cap(dtype):
+    """One rank, n = 1025 > the fused kernels' row cap: the d-sharded
+    geometric median and centered clipping must take their torch formulas
+    on device and agree with the same functions on the CPU copy."""
+    from byzpy_amd.parallel import sharded as S
+
+    X = _rand(1025, 16, dtype, seed=12)
+    Xc = X.cpu()
+    out = S.geometric_median(X, fixed_iters=4)
+    ref = S.geometric_median(Xc, fixed_iters=4)
+    assert out.is_cuda and out.dtype == dtype
+    assert (out.float().cpu() - ref.float()).norm() < 0.05 * max(
+        1.0, ref.float().norm().item()
+    )
+    out = S.centered_clipping(X, c_tau=0.7, M=3)
+    ref = S.centered_clipping(Xc, c_tau=0.7, M=3)
+    assert out.is_cuda and out.dtype == dtype
+    assert (out.float().cpu() - ref.float()).norm() < 0.05 * max(
+        1.0, ref.float().norm().item()
+    )
