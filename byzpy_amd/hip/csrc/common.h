@@ -16,16 +16,25 @@ DEV float wave_reduce_sum(float v) {
 
 // Block-wide sum; result valid in thread 0. `lds` must hold >= blockDim/64
 // floats. Callers sync before reuse.
-DEV float block_reduce_sum(float v, float* lds) {
+// This form takes the block's wave count from the caller: hipcc folds
+// blockDim.x to the launch's block size only where the kernel body itself
+// reads it, so a device function that reduces many times has its kernel
+// pass block_waves() in (see rowops.hip).
+DEV float block_reduce_sum(float v, float* lds, int nw) {
   const int lane = threadIdx.x & 63;
   const int wid = threadIdx.x >> 6;
   v = wave_reduce_sum(v);
   if (lane == 0) lds[wid] = v;
   __syncthreads();
-  const int nw = (blockDim.x + 63) >> 6;
   v = (threadIdx.x < (unsigned)nw) ? lds[threadIdx.x] : 0.0f;
   if (wid == 0) v = wave_reduce_sum(v);
   return v;
+}
+
+DEV int block_waves() { return (blockDim.x + 63) >> 6; }
+
+DEV float block_reduce_sum(float v, float* lds) {
+  return block_reduce_sum(v, lds, block_waves());
 }
 
 // -- dtype conversion -------------------------------------------------------

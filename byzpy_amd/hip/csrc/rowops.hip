@@ -1,12 +1,24 @@
-// Row/column primitives:
-//   row_sqnorms        (n,d) -> (n,)   per-row ||x||^2, split over k-slabs
-//   row_center_sqdists (n,d),(d,) -> (n,)  per-row ||x - z||^2
-//   row_scale          (n,d),(n,) -> (n,d) row scaling (clip apply)
+// Row/column primitives, by binding and kernel:
+//   row_sqnorms        (n,d) -> (n,)        per-row ||x||^2   row_red_kernel
+//   row_center_sqdists (n,d),(d,) -> (n,)   per-row ||x - z||^2
+//                                           center_sqdists_group_kernel
+//   row_scale          (n,d),(n,) -> (n,d)  row scaling (clip apply)
+//                                           row_scale_kernel
 //   mean_rows          gather-mean of selected rows -> (d,)
 //   group_mean_rows    per-group gather-mean -> (g,d)   (NNM mixing)
+//                                           gather_mean_kernel (both)
 //   bucket_mean        permuted segmented mean -> (nb,d) (Bucketing)
-//   weiszfeld_update   fused w=1/max(dist,eps); z' = sum(w x)/sum(w); ||dz||^2
-//   cc_update          fused alpha=min(1,c/dist); v' = v + sum(alpha (x-v))/n
+//                                           bucket_mean_kernel
+//   weiszfeld_iter/_apply  w=1/max(dist,eps); z' = sum(w x)/sum(w); ||dz||^2
+//                                           weiszfeld_update_kernel
+//   weiszfeld_iter_grouped the same for G independent (m,d) problems
+//       center_sqdists_grouped_kernel + weiszfeld_update_grouped_kernel
+//   cc_iter/_apply     alpha=min(1,c/dist); v' = v + sum(alpha (x-v))/n
+//                                           cc_update_kernel
+//   caf_matvec         s_i = sum_j (x_ij - mu_j) v_j
+//                                           caf_matvec_group_kernel
+//   caf_colsum         t_j = scale * sum_i a_i (x_ij - mu_j)
+//                                           caf_colsum_kernel
 //
 // All kernels are HBM-bound; loads are vectorized to 16 B/lane (f32x4 /
 // bf16x8 — guide G13: hipcc does not auto-vectorize bf16) with a scalar
@@ -14,6 +26,15 @@
 // 2D grid (k-slab, row) + block reduce + one f32 atomic per block (G12).
 // Column kernels: V consecutive coordinates per thread, row loop inside;
 // per-row weights (1/dist etc.) are staged once in LDS per block.
+//
+// Two loop nests carry nine of the eleven kernels and are written once:
+// col_wsum (weighted column sum) and row_group_reduce (per-row reduction of
+// a group of rows against shared f32 operands). Two paths stay outside on
+// purpose, each with its reason next to it: cc_update's scalar path (another
+// expression) and caf_colsum's vector path (bit-equality). Whatever depends
+// on the launch geometry (start, stride, block size, wave count) is computed
+// in the kernel body and passed in: hipcc folds blockDim.x to the plain block
+// size only there, and reads it again per use inside a device function.
 #include "common.h"
 #include "launchers.h"
 #include <type_traits>
@@ -66,6 +87,160 @@ struct VecTraits<__hip_bfloat16> {
     v.z = pack(o[4]) | ((unsigned)pack(o[5]) << 16);
     v.w = pack(o[6]) | ((unsigned)pack(o[7]) << 16);
     *reinterpret_cast<uint4*>(p) = v;
+  }
+};
+
+// -- weighted column sum -----------------------------------------------------
+// out[j] = fin(j, sum_{i in [lo, hi)} wt(i) * X[row(i), j]) for the columns
+// of this thread: V consecutive coordinates per grid-stride step when VEC,
+// else one. row(i) maps the loop index to a row of X, wt(i) is its f32
+// weight (a constant 1.0f folds away), fin(j, acc) finishes coordinate j.
+// Association is fixed: (w0 x0 + w1 x1) + (w2 x2 + w3 x3) per 4 rows, then
+// a one-row tail.
+
+template <typename T, bool VEC, typename O, typename Row, typename Wt,
+          typename Fin>
+DEV void col_wsum(const T* __restrict__ X, O* __restrict__ out, long d,
+                  long start, long stride, int lo, int hi, Row row, Wt wt,
+                  Fin fin) {
+  if constexpr (VEC) {
+    constexpr int V = VecTraits<T>::V;
+    const long dv = d / V;
+    for (long jv = start; jv < dv; jv += stride) {
+      float acc[V] = {0};
+      // 4 independent row loads in flight per step (a single runtime-n
+      // loop leaves one load outstanding and goes latency-bound)
+      int i = lo;
+      for (; i + 4 <= hi; i += 4) {
+        float x0[V], x1[V], x2[V], x3[V];
+        VecTraits<T>::load(X + (long)row(i + 0) * d + jv * V, x0);
+        VecTraits<T>::load(X + (long)row(i + 1) * d + jv * V, x1);
+        VecTraits<T>::load(X + (long)row(i + 2) * d + jv * V, x2);
+        VecTraits<T>::load(X + (long)row(i + 3) * d + jv * V, x3);
+        const float w0 = wt(i), w1 = wt(i + 1), w2 = wt(i + 2), w3 = wt(i + 3);
+#pragma unroll
+        for (int c = 0; c < V; ++c)
+          acc[c] += (w0 * x0[c] + w1 * x1[c]) + (w2 * x2[c] + w3 * x3[c]);
+      }
+      for (; i < hi; ++i) {
+        const float w = wt(i);
+        float x[V];
+        VecTraits<T>::load(X + (long)row(i) * d + jv * V, x);
+#pragma unroll
+        for (int c = 0; c < V; ++c) acc[c] += w * x[c];
+      }
+      if constexpr (std::is_same<O, float>::value) {
+#pragma unroll
+        for (int c = 0; c < V; ++c) out[jv * V + c] = fin(jv * V + c, acc[c]);
+      } else {  // bf16 results: one packed 16 B store
+#pragma unroll
+        for (int c = 0; c < V; ++c) acc[c] = fin(jv * V + c, acc[c]);
+        VecTraits<O>::store(out + jv * V, acc);
+      }
+    }
+  } else {
+    for (long j = start; j < d; j += stride) {
+      float acc = 0.0f;
+      for (int i = lo; i < hi; ++i)
+        acc += wt(i) * to_f<T>(X[(long)row(i) * d + j]);
+      out[j] = from_f<O>(fin(j, acc));
+    }
+  }
+}
+
+// Stages w(i), i < n, in w_lds once per block of nthreads threads; returns
+// sum_i w(i) in every thread (summed in row order).
+template <typename W>
+DEV float stage_weights(float* w_lds, int n, unsigned nthreads, W w) {
+  for (int i = threadIdx.x; i < n; i += nthreads) w_lds[i] = w(i);
+  __syncthreads();
+  float sum = 0.0f;
+  for (int i = 0; i < n; ++i) sum += w_lds[i];
+  return sum;
+}
+
+// -- row-group reduction -----------------------------------------------------
+// out[i] += sum_j term(Xg[i, j], f_0[j], .., f_{K-1}[j]) for the `rows` <=
+// DIST_GROUP rows of one block. The K f32 operand vectors (a center z; or
+// mu and v) are read once per column step and shared by the whole group
+// instead of once per row — at small n the f32 center dominates traffic
+// (n=8 bf16: z re-reads were 2/3 of all bytes). One block reduction and one
+// atomic per row; nw is the kernel's block_waves().
+
+constexpr int DIST_GROUP = 32;  // rows per block (blockIdx.y = group of 32)
+
+template <typename T, bool VEC, int K, typename Term>
+DEV void row_group_reduce(const T* __restrict__ Xg,
+                          const float* const (&ops)[K],
+                          float* __restrict__ out, int rows, long d,
+                          long start, long stride, int nw, Term term) {
+  __shared__ float lds[DIST_GROUP][16];
+  float acc[DIST_GROUP] = {0};
+  if constexpr (VEC) {
+    constexpr int V = VecTraits<T>::V;
+    const long dv = d / V;
+    for (long jv = start; jv < dv; jv += stride) {
+      float f[V][K];
+      {
+        // operands are f32; load V floats as V/4 float4s
+        float tmp[4];
+#pragma unroll
+        for (int q4 = 0; q4 < V / 4; ++q4) {
+#pragma unroll
+          for (int k = 0; k < K; ++k) {
+            VecTraits<float>::load(ops[k] + jv * V + q4 * 4, tmp);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) f[q4 * 4 + c][k] = tmp[c];
+          }
+        }
+      }
+      // full groups of 4 rows keep 4 loads in flight
+      int i = 0;
+      for (; i + 4 <= rows; i += 4) {
+        float x0[V], x1[V], x2[V], x3[V];
+        VecTraits<T>::load(Xg + (long)(i + 0) * d + jv * V, x0);
+        VecTraits<T>::load(Xg + (long)(i + 1) * d + jv * V, x1);
+        VecTraits<T>::load(Xg + (long)(i + 2) * d + jv * V, x2);
+        VecTraits<T>::load(Xg + (long)(i + 3) * d + jv * V, x3);
+#pragma unroll
+        for (int c = 0; c < V; ++c) {
+          acc[i + 0] += term(x0[c], f[c]);
+          acc[i + 1] += term(x1[c], f[c]);
+          acc[i + 2] += term(x2[c], f[c]);
+          acc[i + 3] += term(x3[c], f[c]);
+        }
+      }
+      for (; i < rows; ++i) {
+        float x[V];
+        VecTraits<T>::load(Xg + (long)i * d + jv * V, x);
+#pragma unroll
+        for (int c = 0; c < V; ++c) acc[i] += term(x[c], f[c]);
+      }
+    }
+  } else {
+    for (long j = start; j < d; j += stride) {
+      float f[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) f[k] = ops[k][j];
+      for (int i = 0; i < rows; ++i)
+        acc[i] += term(to_f<T>(Xg[(long)i * d + j]), f);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < DIST_GROUP; ++i) {
+    if (i < rows) {
+      const float s = block_reduce_sum(acc[i], lds[i], nw);
+      if (threadIdx.x == 0) atomicAdd(&out[i], s);
+    }
+    __syncthreads();
+  }
+}
+
+// (x - z)^2, the term of both center-distance kernels
+struct SqDistTerm {
+  DEV float operator()(float x, const float (&f)[1]) const {
+    const float dd = x - f[0];
+    return dd * dd;
   }
 };
 
@@ -127,161 +302,40 @@ __global__ void row_red_kernel(const T* __restrict__ X,
   if (threadIdx.x == 0) atomicAdd(&out[row], acc);
 }
 
-// -- grouped center distances ----------------------------------------------
-// ||x_i - z||^2 for a GROUP of rows per block (blockIdx.y = group of 8):
-// z is read once per group instead of once per row — at small n the f32
-// center dominates traffic (n=8 bf16: z re-reads were 2/3 of all bytes).
-
-constexpr int DIST_GROUP = 32;
+// -- center distances ---------------------------------------------------------
+// ||x_i - z||^2 for the rows [g0, g0 + DIST_GROUP) of one (n, d) matrix.
 
 template <typename T, bool VEC>
 __global__ void center_sqdists_group_kernel(const T* __restrict__ X,
                                             const float* __restrict__ z,
                                             float* __restrict__ out, int n,
                                             long d) {
-  __shared__ float lds[DIST_GROUP][16];
-  constexpr int V = VecTraits<T>::V;
   const int g0 = blockIdx.y * DIST_GROUP;
-  const int rows = min(DIST_GROUP, n - g0);
-  float acc[DIST_GROUP] = {0};
   const long start = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long stride = (long)gridDim.x * blockDim.x;
-  if (VEC) {
-    const long dv = d / V;
-    for (long jv = start; jv < dv; jv += stride) {
-      float zv[V];
-      {
-        // z is f32; load V floats as V/4 float4s
-        float tmp[4];
-#pragma unroll
-        for (int q4 = 0; q4 < V / 4; ++q4) {
-          VecTraits<float>::load(z + jv * V + q4 * 4, tmp);
-#pragma unroll
-          for (int c = 0; c < 4; ++c) zv[q4 * 4 + c] = tmp[c];
-        }
-      }
-      // full groups of 4 rows keep 4 loads in flight
-      int i = 0;
-      for (; i + 4 <= rows; i += 4) {
-        float x0[V], x1[V], x2[V], x3[V];
-        VecTraits<T>::load(X + (long)(g0 + i + 0) * d + jv * V, x0);
-        VecTraits<T>::load(X + (long)(g0 + i + 1) * d + jv * V, x1);
-        VecTraits<T>::load(X + (long)(g0 + i + 2) * d + jv * V, x2);
-        VecTraits<T>::load(X + (long)(g0 + i + 3) * d + jv * V, x3);
-#pragma unroll
-        for (int c = 0; c < V; ++c) {
-          const float d0 = x0[c] - zv[c], d1 = x1[c] - zv[c];
-          const float d2 = x2[c] - zv[c], d3 = x3[c] - zv[c];
-          acc[i + 0] += d0 * d0;
-          acc[i + 1] += d1 * d1;
-          acc[i + 2] += d2 * d2;
-          acc[i + 3] += d3 * d3;
-        }
-      }
-      for (; i < rows; ++i) {
-        float x[V];
-        VecTraits<T>::load(X + (long)(g0 + i) * d + jv * V, x);
-#pragma unroll
-        for (int c = 0; c < V; ++c) {
-          const float dd = x[c] - zv[c];
-          acc[i] += dd * dd;
-        }
-      }
-    }
-  } else {
-    for (long j = start; j < d; j += stride) {
-      const float zj = z[j];
-      for (int i = 0; i < rows; ++i) {
-        const float dd = to_f<T>(X[(long)(g0 + i) * d + j]) - zj;
-        acc[i] += dd * dd;
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < DIST_GROUP; ++i) {
-    if (i < rows) {
-      const float s = block_reduce_sum(acc[i], lds[i]);
-      if (threadIdx.x == 0) atomicAdd(&out[g0 + i], s);
-    }
-    __syncthreads();
-  }
+  const float* const ops[1] = {z};
+  row_group_reduce<T, VEC>(X + (long)g0 * d, ops, out + g0,
+                           min(DIST_GROUP, n - g0), d, start, stride,
+                           block_waves(), SqDistTerm{});
 }
 
 // -- grouped center distances + Weiszfeld update ---------------------------
 // G independent small aggregation problems per launch (gossip: every
 // node's geomed iteration in ONE kernel pair instead of 2G launches on
-// G streams). blockIdx.y = group; each group has its own center.
+// G streams). blockIdx.y = group; each group has its own center and its
+// m <= DIST_GROUP rows.
 
 template <typename T, bool VEC>
 __global__ void center_sqdists_grouped_kernel(const T* __restrict__ X,
                                               const float* __restrict__ Z,
                                               float* __restrict__ out, int m,
                                               long d) {
-  __shared__ float lds[DIST_GROUP][16];
-  constexpr int V = VecTraits<T>::V;
   const int g = blockIdx.y;
-  const T* Xg = X + (long)g * m * d;
-  const float* z = Z + (long)g * d;
-  float acc[DIST_GROUP] = {0};
   const long start = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long stride = (long)gridDim.x * blockDim.x;
-  if (VEC) {
-    const long dv = d / V;
-    for (long jv = start; jv < dv; jv += stride) {
-      float zv[V];
-      {
-        float tmp[4];
-#pragma unroll
-        for (int q4 = 0; q4 < V / 4; ++q4) {
-          VecTraits<float>::load(z + jv * V + q4 * 4, tmp);
-#pragma unroll
-          for (int c = 0; c < 4; ++c) zv[q4 * 4 + c] = tmp[c];
-        }
-      }
-      int i = 0;
-      for (; i + 4 <= m; i += 4) {  // 4 row loads in flight
-        float x0[V], x1[V], x2[V], x3[V];
-        VecTraits<T>::load(Xg + (long)(i + 0) * d + jv * V, x0);
-        VecTraits<T>::load(Xg + (long)(i + 1) * d + jv * V, x1);
-        VecTraits<T>::load(Xg + (long)(i + 2) * d + jv * V, x2);
-        VecTraits<T>::load(Xg + (long)(i + 3) * d + jv * V, x3);
-#pragma unroll
-        for (int c = 0; c < V; ++c) {
-          const float d0 = x0[c] - zv[c], d1 = x1[c] - zv[c];
-          const float d2 = x2[c] - zv[c], d3 = x3[c] - zv[c];
-          acc[i + 0] += d0 * d0;
-          acc[i + 1] += d1 * d1;
-          acc[i + 2] += d2 * d2;
-          acc[i + 3] += d3 * d3;
-        }
-      }
-      for (; i < m; ++i) {
-        float x[V];
-        VecTraits<T>::load(Xg + (long)i * d + jv * V, x);
-#pragma unroll
-        for (int c = 0; c < V; ++c) {
-          const float dd = x[c] - zv[c];
-          acc[i] += dd * dd;
-        }
-      }
-    }
-  } else {
-    for (long j = start; j < d; j += stride) {
-      const float zj = z[j];
-      for (int i = 0; i < m; ++i) {
-        const float dd = to_f<T>(Xg[(long)i * d + j]) - zj;
-        acc[i] += dd * dd;
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < DIST_GROUP; ++i) {
-    if (i < m) {
-      const float sred = block_reduce_sum(acc[i], lds[i]);
-      if (threadIdx.x == 0) atomicAdd(&out[(long)g * m + i], sred);
-    }
-    __syncthreads();
-  }
+  const float* const ops[1] = {Z + (long)g * d};
+  row_group_reduce<T, VEC>(X + (long)g * m * d, ops, out + (long)g * m, m, d,
+                           start, stride, block_waves(), SqDistTerm{});
 }
 
 template <typename T, bool VEC>
@@ -290,55 +344,18 @@ __global__ void weiszfeld_update_grouped_kernel(
     const float* __restrict__ dist2, float* __restrict__ Z_new, int m, long d,
     float eps) {
   __shared__ float w_lds[DIST_GROUP];
-  constexpr int V = VecTraits<T>::V;
   const int g = blockIdx.y;
-  const T* Xg = X + (long)g * m * d;
-  const float* z = Z + (long)g * d;
-  float* z_new = Z_new + (long)g * d;
-  for (int i = threadIdx.x; i < m; i += blockDim.x)
-    w_lds[i] = 1.0f / fmaxf(sqrtf(dist2[(long)g * m + i]), eps);
-  __syncthreads();
-  float den = 0.0f;
-  for (int i = 0; i < m; ++i) den += w_lds[i];
+  const float* d2 = dist2 + (long)g * m;
+  const float den = stage_weights(w_lds, m, blockDim.x, [&](int i) {
+    return 1.0f / fmaxf(sqrtf(d2[i]), eps);
+  });
   const float inv_den = 1.0f / den;
-
   const long start = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long stride = (long)gridDim.x * blockDim.x;
-  if (VEC) {
-    const long dv = d / V;
-    for (long jv = start; jv < dv; jv += stride) {
-      float num[V] = {0};
-      int i = 0;
-      for (; i + 4 <= m; i += 4) {  // 4 row loads in flight
-        float x0[V], x1[V], x2[V], x3[V];
-        VecTraits<T>::load(Xg + (long)(i + 0) * d + jv * V, x0);
-        VecTraits<T>::load(Xg + (long)(i + 1) * d + jv * V, x1);
-        VecTraits<T>::load(Xg + (long)(i + 2) * d + jv * V, x2);
-        VecTraits<T>::load(Xg + (long)(i + 3) * d + jv * V, x3);
-        const float w0 = w_lds[i], w1 = w_lds[i + 1], w2 = w_lds[i + 2],
-                    w3 = w_lds[i + 3];
-#pragma unroll
-        for (int c = 0; c < V; ++c)
-          num[c] += (w0 * x0[c] + w1 * x1[c]) + (w2 * x2[c] + w3 * x3[c]);
-      }
-      for (; i < m; ++i) {
-        const float w = w_lds[i];
-        float x[V];
-        VecTraits<T>::load(Xg + (long)i * d + jv * V, x);
-#pragma unroll
-        for (int c = 0; c < V; ++c) num[c] += w * x[c];
-      }
-#pragma unroll
-      for (int c = 0; c < V; ++c) z_new[jv * V + c] = num[c] * inv_den;
-    }
-  } else {
-    for (long j = start; j < d; j += stride) {
-      float num = 0.0f;
-      for (int i = 0; i < m; ++i)
-        num += w_lds[i] * to_f<T>(Xg[(long)i * d + j]);
-      z_new[j] = num * inv_den;
-    }
-  }
+  col_wsum<T, VEC>(
+      X + (long)g * m * d, Z_new + (long)g * d, d, start, stride, 0, m,
+      [](int i) { return i; }, [&](int i) { return w_lds[i]; },
+      [&](long, float num) { return num * inv_den; });
 }
 
 // -- row scaling ------------------------------------------------------------
@@ -377,91 +394,31 @@ template <typename T, bool VEC, bool GROUPED>
 __global__ void gather_mean_kernel(const T* __restrict__ X,
                                    const int* __restrict__ idx, int k,
                                    T* __restrict__ out, long d) {
-  constexpr int V = VecTraits<T>::V;
   const int g = GROUPED ? blockIdx.y : 0;
   const int* gi = idx + (long)g * k;
-  T* og = out + (long)g * d;
   const float inv = 1.0f / (float)k;
   const long start = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long stride = (long)gridDim.x * blockDim.x;
-  if (VEC) {
-    const long dv = d / V;
-    for (long jv = start; jv < dv; jv += stride) {
-      float acc[V] = {0};
-      // 4 independent row loads in flight per step (a single runtime-n
-      // loop leaves one load outstanding and goes latency-bound)
-      int i = 0;
-      for (; i + 4 <= k; i += 4) {
-        float x0[V], x1[V], x2[V], x3[V];
-        VecTraits<T>::load(X + (long)gi[i + 0] * d + jv * V, x0);
-        VecTraits<T>::load(X + (long)gi[i + 1] * d + jv * V, x1);
-        VecTraits<T>::load(X + (long)gi[i + 2] * d + jv * V, x2);
-        VecTraits<T>::load(X + (long)gi[i + 3] * d + jv * V, x3);
-#pragma unroll
-        for (int c = 0; c < V; ++c) acc[c] += (x0[c] + x1[c]) + (x2[c] + x3[c]);
-      }
-      for (; i < k; ++i) {
-        float x[V];
-        VecTraits<T>::load(X + (long)gi[i] * d + jv * V, x);
-#pragma unroll
-        for (int c = 0; c < V; ++c) acc[c] += x[c];
-      }
-#pragma unroll
-      for (int c = 0; c < V; ++c) acc[c] *= inv;
-      VecTraits<T>::store(og + jv * V, acc);
-    }
-  } else {
-    for (long j = start; j < d; j += stride) {
-      float acc = 0.0f;
-      for (int i = 0; i < k; ++i) acc += to_f<T>(X[(long)gi[i] * d + j]);
-      og[j] = from_f<T>(acc * inv);
-    }
-  }
+  col_wsum<T, VEC>(
+      X, out + (long)g * d, d, start, stride, 0, k,
+      [&](int i) { return gi[i]; }, [](int) { return 1.0f; },
+      [&](long, float acc) { return acc * inv; });
 }
 
 template <typename T, bool VEC>
 __global__ void bucket_mean_kernel(const T* __restrict__ X,
                                    const int* __restrict__ perm, int n,
                                    int bucket, T* __restrict__ out, long d) {
-  constexpr int V = VecTraits<T>::V;
   const int b = blockIdx.y;
   const int lo = b * bucket;
   const int hi = min(n, lo + bucket);
-  T* ob = out + (long)b * d;
   const float inv = 1.0f / (float)(hi - lo);
   const long start = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long stride = (long)gridDim.x * blockDim.x;
-  if (VEC) {
-    const long dv = d / V;
-    for (long jv = start; jv < dv; jv += stride) {
-      float acc[V] = {0};
-      int i = lo;
-      for (; i + 4 <= hi; i += 4) {
-        float x0[V], x1[V], x2[V], x3[V];
-        VecTraits<T>::load(X + (long)perm[i + 0] * d + jv * V, x0);
-        VecTraits<T>::load(X + (long)perm[i + 1] * d + jv * V, x1);
-        VecTraits<T>::load(X + (long)perm[i + 2] * d + jv * V, x2);
-        VecTraits<T>::load(X + (long)perm[i + 3] * d + jv * V, x3);
-#pragma unroll
-        for (int c = 0; c < V; ++c) acc[c] += (x0[c] + x1[c]) + (x2[c] + x3[c]);
-      }
-      for (; i < hi; ++i) {
-        float x[V];
-        VecTraits<T>::load(X + (long)perm[i] * d + jv * V, x);
-#pragma unroll
-        for (int c = 0; c < V; ++c) acc[c] += x[c];
-      }
-#pragma unroll
-      for (int c = 0; c < V; ++c) acc[c] *= inv;
-      VecTraits<T>::store(ob + jv * V, acc);
-    }
-  } else {
-    for (long j = start; j < d; j += stride) {
-      float acc = 0.0f;
-      for (int i = lo; i < hi; ++i) acc += to_f<T>(X[(long)perm[i] * d + j]);
-      ob[j] = from_f<T>(acc * inv);
-    }
-  }
+  col_wsum<T, VEC>(
+      X, out + (long)b * d, d, start, stride, lo, hi,
+      [&](int i) { return perm[i]; }, [](int) { return 1.0f; },
+      [&](long, float acc) { return acc * inv; });
 }
 
 // -- fused fixed-point iterations ------------------------------------------
@@ -477,60 +434,22 @@ __global__ void weiszfeld_update_kernel(const T* __restrict__ X,
                                         long d, float eps) {
   __shared__ float w_lds[MAX_N_LDS];
   __shared__ float red[16];
-  constexpr int V = VecTraits<T>::V;
-  for (int i = threadIdx.x; i < n; i += blockDim.x)
-    w_lds[i] = 1.0f / fmaxf(sqrtf(dist2[i]), eps);
-  __syncthreads();
-  float den = 0.0f;
-  for (int i = 0; i < n; ++i) den += w_lds[i];
+  const float den = stage_weights(w_lds, n, blockDim.x, [&](int i) {
+    return 1.0f / fmaxf(sqrtf(dist2[i]), eps);
+  });
   const float inv_den = 1.0f / den;
-
   float local_shift = 0.0f;
   const long start = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long stride = (long)gridDim.x * blockDim.x;
-  if (VEC) {
-    const long dv = d / V;
-    for (long jv = start; jv < dv; jv += stride) {
-      float num[V] = {0};
-      int i = 0;
-      for (; i + 4 <= n; i += 4) {
-        float x0[V], x1[V], x2[V], x3[V];
-        VecTraits<T>::load(X + (long)(i + 0) * d + jv * V, x0);
-        VecTraits<T>::load(X + (long)(i + 1) * d + jv * V, x1);
-        VecTraits<T>::load(X + (long)(i + 2) * d + jv * V, x2);
-        VecTraits<T>::load(X + (long)(i + 3) * d + jv * V, x3);
-        const float w0 = w_lds[i], w1 = w_lds[i + 1], w2 = w_lds[i + 2],
-                    w3 = w_lds[i + 3];
-#pragma unroll
-        for (int c = 0; c < V; ++c)
-          num[c] += (w0 * x0[c] + w1 * x1[c]) + (w2 * x2[c] + w3 * x3[c]);
-      }
-      for (; i < n; ++i) {
-        const float w = w_lds[i];
-        float x[V];
-        VecTraits<T>::load(X + (long)i * d + jv * V, x);
-#pragma unroll
-        for (int c = 0; c < V; ++c) num[c] += w * x[c];
-      }
-#pragma unroll
-      for (int c = 0; c < V; ++c) {
-        const float zi = num[c] * inv_den;
-        const float dz = zi - z[jv * V + c];
+  col_wsum<T, VEC>(
+      X, z_new, d, start, stride, 0, n, [](int i) { return i; },
+      [&](int i) { return w_lds[i]; },
+      [&](long j, float num) {
+        const float zi = num * inv_den;
+        const float dz = zi - z[j];
         local_shift += dz * dz;
-        z_new[jv * V + c] = zi;
-      }
-    }
-  } else {
-    for (long j = start; j < d; j += stride) {
-      float num = 0.0f;
-      for (int i = 0; i < n; ++i)
-        num += w_lds[i] * to_f<T>(X[(long)i * d + j]);
-      const float zi = num * inv_den;
-      const float dz = zi - z[j];
-      local_shift += dz * dz;
-      z_new[j] = zi;
-    }
-  }
+        return zi;
+      });
   const float s = block_reduce_sum(local_shift, red);
   if (threadIdx.x == 0) atomicAdd(shift2, s);
 }
@@ -542,47 +461,24 @@ __global__ void cc_update_kernel(const T* __restrict__ X,
                                  float* __restrict__ v_new, int n, long d,
                                  float c_tau, float eps) {
   __shared__ float a_lds[MAX_N_LDS];
-  constexpr int V = VecTraits<T>::V;
-  for (int i = threadIdx.x; i < n; i += blockDim.x)
-    a_lds[i] = fminf(1.0f, c_tau / fmaxf(sqrtf(dist2[i]), eps));
-  __syncthreads();
-  float alpha_sum = 0.0f;
-  for (int i = 0; i < n; ++i) alpha_sum += a_lds[i];
+  const float alpha_sum = stage_weights(a_lds, n, blockDim.x, [&](int i) {
+    return fminf(1.0f, c_tau / fmaxf(sqrtf(dist2[i]), eps));
+  });
   const float inv_n = 1.0f / (float)n;
-
   const long start = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long stride = (long)gridDim.x * blockDim.x;
-  if (VEC) {
-    const long dv = d / V;
-    for (long jv = start; jv < dv; jv += stride) {
-      float acc[V] = {0};
-      int i = 0;
-      for (; i + 4 <= n; i += 4) {
-        float x0[V], x1[V], x2[V], x3[V];
-        VecTraits<T>::load(X + (long)(i + 0) * d + jv * V, x0);
-        VecTraits<T>::load(X + (long)(i + 1) * d + jv * V, x1);
-        VecTraits<T>::load(X + (long)(i + 2) * d + jv * V, x2);
-        VecTraits<T>::load(X + (long)(i + 3) * d + jv * V, x3);
-        const float a0 = a_lds[i], a1 = a_lds[i + 1], a2 = a_lds[i + 2],
-                    a3 = a_lds[i + 3];
-#pragma unroll
-        for (int c = 0; c < V; ++c)
-          acc[c] += (a0 * x0[c] + a1 * x1[c]) + (a2 * x2[c] + a3 * x3[c]);
-      }
-      for (; i < n; ++i) {
-        const float a = a_lds[i];
-        float x[V];
-        VecTraits<T>::load(X + (long)i * d + jv * V, x);
-#pragma unroll
-        for (int c = 0; c < V; ++c) acc[c] += a * x[c];
-      }
-#pragma unroll
-      for (int c = 0; c < V; ++c) {
-        const float vj = v[jv * V + c];
-        v_new[jv * V + c] = vj + (acc[c] - alpha_sum * vj) * inv_n;
-      }
-    }
+  if constexpr (VEC) {
+    // sum(alpha (x - v)) = sum(alpha x) - alpha_sum v: v leaves the row loop
+    col_wsum<T, true>(
+        X, v_new, d, start, stride, 0, n, [](int i) { return i; },
+        [&](int i) { return a_lds[i]; },
+        [&](long j, float acc) {
+          const float vj = v[j];
+          return vj + (acc - alpha_sum * vj) * inv_n;
+        });
   } else {
+    // the scalar path subtracts v per row: another expression, another
+    // rounding, kept as it is
     for (long j = start; j < d; j += stride) {
       const float vj = v[j];
       float acc = 0.0f;
@@ -605,66 +501,14 @@ __global__ void caf_matvec_group_kernel(const T* __restrict__ X,
                                         const float* __restrict__ v,
                                         float* __restrict__ out, int n,
                                         long d) {
-  __shared__ float lds[DIST_GROUP][16];
-  constexpr int V = VecTraits<T>::V;
   const int g0 = blockIdx.y * DIST_GROUP;
-  const int rows = min(DIST_GROUP, n - g0);
-  float acc[DIST_GROUP] = {0};
   const long start = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long stride = (long)gridDim.x * blockDim.x;
-  if (VEC) {
-    const long dv = d / V;
-    for (long jv = start; jv < dv; jv += stride) {
-      float muv[V], vv[V];
-      {
-        float tmp[4];
-#pragma unroll
-        for (int q4 = 0; q4 < V / 4; ++q4) {
-          VecTraits<float>::load(mu + jv * V + q4 * 4, tmp);
-#pragma unroll
-          for (int c = 0; c < 4; ++c) muv[q4 * 4 + c] = tmp[c];
-          VecTraits<float>::load(v + jv * V + q4 * 4, tmp);
-#pragma unroll
-          for (int c = 0; c < 4; ++c) vv[q4 * 4 + c] = tmp[c];
-        }
-      }
-      int i = 0;
-      for (; i + 4 <= rows; i += 4) {
-        float x0[V], x1[V], x2[V], x3[V];
-        VecTraits<T>::load(X + (long)(g0 + i + 0) * d + jv * V, x0);
-        VecTraits<T>::load(X + (long)(g0 + i + 1) * d + jv * V, x1);
-        VecTraits<T>::load(X + (long)(g0 + i + 2) * d + jv * V, x2);
-        VecTraits<T>::load(X + (long)(g0 + i + 3) * d + jv * V, x3);
-#pragma unroll
-        for (int c = 0; c < V; ++c) {
-          acc[i + 0] += (x0[c] - muv[c]) * vv[c];
-          acc[i + 1] += (x1[c] - muv[c]) * vv[c];
-          acc[i + 2] += (x2[c] - muv[c]) * vv[c];
-          acc[i + 3] += (x3[c] - muv[c]) * vv[c];
-        }
-      }
-      for (; i < rows; ++i) {
-        float x[V];
-        VecTraits<T>::load(X + (long)(g0 + i) * d + jv * V, x);
-#pragma unroll
-        for (int c = 0; c < V; ++c) acc[i] += (x[c] - muv[c]) * vv[c];
-      }
-    }
-  } else {
-    for (long j = start; j < d; j += stride) {
-      const float mj = mu[j], vj = v[j];
-      for (int i = 0; i < rows; ++i)
-        acc[i] += (to_f<T>(X[(long)(g0 + i) * d + j]) - mj) * vj;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < DIST_GROUP; ++i) {
-    if (i < rows) {
-      const float s = block_reduce_sum(acc[i], lds[i]);
-      if (threadIdx.x == 0) atomicAdd(&out[g0 + i], s);
-    }
-    __syncthreads();
-  }
+  const float* const ops[2] = {mu, v};
+  row_group_reduce<T, VEC>(
+      X + (long)g0 * d, ops, out + g0, min(DIST_GROUP, n - g0), d, start,
+      stride, block_waves(),
+      [](float x, const float (&f)[2]) { return (x - f[0]) * f[1]; });
 }
 
 // sum_i a_i X_ij - mu_j * sum_i a_i, scaled: the mu subtraction factors out
@@ -678,16 +522,18 @@ __global__ void caf_colsum_kernel(const T* __restrict__ X,
                                   const float* __restrict__ scale,
                                   float* __restrict__ out, int n, long d) {
   __shared__ float a_lds[MAX_N_LDS];
-  constexpr int V = VecTraits<T>::V;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) a_lds[i] = a[i];
-  __syncthreads();
-  float a_sum = 0.0f;
-  for (int i = 0; i < n; ++i) a_sum += a_lds[i];
+  const float a_sum =
+      stage_weights(a_lds, n, blockDim.x, [&](int i) { return a[i]; });
   const float sc = scale ? *scale : 1.0f;
-
   const long start = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long stride = (long)gridDim.x * blockDim.x;
-  if (VEC) {
+  if constexpr (VEC) {
+    // Not through col_wsum: with the nullable mu, hipcc fuses a_sum * m into
+    // the subtraction for only some of the V coordinates, and which ones
+    // changes with the shape of the surrounding code; through the skeleton
+    // the low bits of t_j moved. This copy stays until a change that may
+    // move them.
+    constexpr int V = VecTraits<T>::V;
     const long dv = d / V;
     for (long jv = start; jv < dv; jv += stride) {
       float acc[V] = {0};
@@ -718,13 +564,13 @@ __global__ void caf_colsum_kernel(const T* __restrict__ X,
       }
     }
   } else {
-    for (long j = start; j < d; j += stride) {
-      float acc = 0.0f;
-      for (int i = 0; i < n; ++i)
-        acc += a_lds[i] * to_f<T>(X[(long)i * d + j]);
-      const float m = mu ? mu[j] : 0.0f;
-      out[j] = (acc - a_sum * m) * sc;
-    }
+    col_wsum<T, false>(
+        X, out, d, start, stride, 0, n, [](int i) { return i; },
+        [&](int i) { return a_lds[i]; },
+        [&](long j, float acc) {
+          const float m = mu ? mu[j] : 0.0f;
+          return (acc - a_sum * m) * sc;
+        });
   }
 }
 

@@ -1095,6 +1095,137 @@ def test_binding_grouped_weiszfeld_small(dtype, d):
     assert torch.allclose(out.cpu(), expect, **_tol(dtype))
 
 
+# -- rowops loop nests beyond the n = 5 cases ---------------------------------
+# The cases above use n = 5 and 3-entry index lists, so the column-sum
+# kernels only run their one-row tail loop there and the row-group kernels
+# see a single group. These reach the 4-row unrolled block plus a tail
+# through every row map, a second row group (37 = 32 + 4 + 1), every
+# accumulator slot of the grouped path (m = 32), and a second column
+# grid-stride step (more than 4096 blocks x 256 threads of work).
+
+_IDX6 = [7, 0, 3, 8, 3, 5]  # 4 + 2, row 3 twice
+_GIDX_3x5 = [[0, 1, 2, 3, 4], [8, 8, 2, 6, 1], [5, 7, 0, 4, 4]]
+_GIDX_5x5 = _GIDX_3x5 + [[6, 3, 1, 8, 0], [2, 2, 2, 7, 5]]  # g > 4: other grid
+_PERM9 = [4, 0, 8, 2, 6, 1, 7, 3, 5]  # bucket = 5 -> buckets of 5 and 4
+
+
+def _i32(v):
+    return torch.tensor(v, dtype=torch.int32, device="cuda")
+
+
+_INDEX_MAP_CASES = {
+    "mean_rows": (
+        lambda e, X: e.mean_rows(X, _i32(_IDX6)),
+        lambda Xf: Xf[_IDX6].mean(dim=0)),
+    "group_mean_rows_3x5": (
+        lambda e, X: e.group_mean_rows(X, _i32(_GIDX_3x5)),
+        lambda Xf: Xf[torch.tensor(_GIDX_3x5)].mean(dim=1)),
+    "group_mean_rows_5x5": (
+        lambda e, X: e.group_mean_rows(X, _i32(_GIDX_5x5)),
+        lambda Xf: Xf[torch.tensor(_GIDX_5x5)].mean(dim=1)),
+    "bucket_mean": (
+        lambda e, X: e.bucket_mean(X, _i32(_PERM9), 5),
+        lambda Xf: F.bucketing(Xf, 5, _PERM9)),
+}
+
+
+@pytest.fixture(scope="module")
+def rowops_inputs():
+    """(n, d, dtype) -> (X on device, X.float() on CPU) for n = 9 and n = 37;
+    built once, never modified."""
+    out = {}
+    for n in (9, 37):
+        for d in (33, 64):
+            for dtype in DTYPES:
+                X = _rand(n, d, dtype, seed=_SMALL_SEED + n)
+                out[n, d, dtype] = (X, X.float().cpu())
+    return out
+
+
+def _assert_close(out, expect, dtype, what):
+    assert out.shape == expect.shape, what
+    err = (out.float().cpu() - expect).abs().max().item()
+    print(f"{what}: max err {err:.3e}")
+    assert torch.allclose(out.float().cpu(), expect, **_tol(dtype)), (
+        f"{what}: max err {err:.3e}")
+
+
+@pytest.mark.parametrize("d", [33, 64])
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("op", sorted(_INDEX_MAP_CASES))
+def test_binding_index_maps_unrolled_block_plus_tail(rowops_inputs, op, dtype, d):
+    from byzpy_amd.hip import require
+
+    X, Xf = rowops_inputs[9, d, dtype]
+    run, ref = _INDEX_MAP_CASES[op]
+    _assert_close(run(require(), X), ref(Xf), dtype, f"{op} n=9 d={d} {dtype}")
+
+
+@pytest.mark.parametrize("m,d", [(6, 33), (6, 64), (32, 33), (32, 64)])
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_binding_grouped_weiszfeld_unrolled_and_full_group(dtype, m, d):
+    """G = 2 groups of m = 6 (4 + 2) rows, and of m = 32, the grouped
+    path's cap, where every accumulator slot is live."""
+    from byzpy_amd.hip import require
+
+    g = torch.Generator().manual_seed(_SMALL_SEED + m)
+    X3 = torch.randn(2, m, d, generator=g).to("cuda", dtype)
+    Z = torch.randn(2, d, generator=g)
+    out = require().weiszfeld_iter_grouped(X3, Z.cuda(), 1e-12)
+    X3f = X3.float().cpu()
+    expect = torch.stack([_wz_step(X3f[i], Z[i]) for i in range(2)])
+    _assert_close(out, expect, dtype, f"weiszfeld_iter_grouped m={m} d={d} {dtype}")
+
+
+@pytest.mark.parametrize("d", [33, 64])
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("op", ["row_center_sqdists", "caf_matvec"])
+def test_binding_row_group_boundary(rowops_inputs, op, dtype, d):
+    """n = 37: two row groups, the second with 4 + 1 rows."""
+    from byzpy_amd.hip import require
+
+    X, Xf = rowops_inputs[37, d, dtype]
+    g = torch.Generator().manual_seed(_SMALL_SEED + d)
+    z = torch.randn(d, generator=g)
+    v = torch.randn(d, generator=g)
+    if op == "row_center_sqdists":
+        out = require().row_center_sqdists(X, z.cuda())
+        expect = ((Xf - z[None, :]) ** 2).sum(dim=1)
+    else:
+        out = require().caf_matvec(X, z.cuda(), v.cuda())
+        expect = (Xf - z[None, :]) @ v
+    _assert_close(out, expect, dtype, f"{op} n=37 d={d} {dtype}")
+
+
+_COL_THREADS = 4096 * 256  # col_grid's cap: one column step covers this many
+
+
+@pytest.mark.parametrize(
+    "op,dtype,d",
+    [
+        ("mean_rows", torch.bfloat16, 8 * _COL_THREADS + 8 * 256),
+        ("caf_colsum_plain", torch.float32, 4 * _COL_THREADS + 4 * 256),
+        ("caf_colsum_plain", torch.float32, _COL_THREADS + 257),  # scalar path
+    ],
+)
+def test_binding_column_grid_stride_wrap(op, dtype, d):
+    """More work items than col_grid's 4096 x 256 threads: the first threads
+    take a second column step."""
+    from byzpy_amd.hip import require
+
+    X = _rand(_SMALL_N, d, dtype, seed=_SMALL_SEED)
+    Xf = X.float().cpu()
+    if op == "mean_rows":
+        idx = [3, 0, 4]
+        out = require().mean_rows(X, _i32(idx))
+        expect = Xf[idx].mean(dim=0)
+    else:
+        s = torch.rand(_SMALL_N, generator=torch.Generator().manual_seed(d)) + 0.5
+        out = require().caf_colsum(X, s.cuda())
+        expect = (s[:, None] * Xf).sum(dim=0)
+    _assert_close(out, expect, dtype, f"{op} n={_SMALL_N} d={d} {dtype}")
+
+
 def test_lds_row_cap_rejected_by_every_lds_staging_binding():
     """weiszfeld_update / cc_update / caf_colsum stage one weight per row in
     a 1024-float LDS array: all five bindings that launch them must refuse
