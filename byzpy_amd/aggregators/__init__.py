@@ -5,6 +5,7 @@ from byzpy_amd.aggregators.coordinate_wise import (
     MeanOfMedians,
 )
 from byzpy_amd.aggregators.geometric_wise import (
+    Bulyan,
     GeometricMedian,
     Krum,
     MinimumDiameterAveraging,
@@ -25,6 +26,7 @@ __all__ = [
     "MeanOfMedians",
     "MultiKrum",
     "Krum",
+    "Bulyan",
     "GeometricMedian",
     "MinimumDiameterAveraging",
     "MoNNA",

@@ -83,6 +83,61 @@ class Krum(MultiKrum):
             self._cleanup(handles)
 
 
+class Bulyan(Aggregator):
+    """Bulyan (El Mhamdi, Guerraoui, Rouault 2018): n - 2f rows chosen by
+    iterated Krum, then per coordinate the mean of the n - 4f selected
+    values closest to their median. Needs n >= 4f + 3. Row-chunked Gram on
+    CPU pools; Gram + one selection launch + one indexed column launch on
+    GPU."""
+
+    name = "bulyan"
+    supports_subtasks = True
+    max_subtasks_inflight = 0
+
+    def __init__(self, f: int, *, chunk_size: int = 32) -> None:
+        if f < 0:
+            raise ValueError("f must be >= 0")
+        self.f = int(f)
+        self.chunk_size = int(chunk_size)
+
+    def _check(self, n: int) -> None:
+        if n < 4 * self.f + 3:
+            raise ValueError(
+                f"Bulyan needs n >= 4f + 3, got n={n}, f={self.f}"
+            )
+
+    def _aggregate(self, X: torch.Tensor) -> torch.Tensor:
+        self._check(X.shape[0])
+        return D.bulyan(X, self.f)
+
+    def create_subtasks(self, ctx: OpContext, **inputs: Any) -> Sequence[SubTask]:
+        gradients = inputs[self.input_key]
+        ref, X, like, handles = self._matrix_ref(ctx, gradients)
+        if X.is_cuda:
+            return []
+        n = X.shape[0]
+        try:
+            self._check(n)
+        except ValueError:
+            self._cleanup(handles)
+            raise
+        ctx.metadata["_op_pending"] = (X, like, handles)
+        chunk = max(1, min(self.chunk_size, n))
+        return [
+            SubTask(fn=SF.gram_row_chunk, args=(ref, lo, hi), name=f"gram[{lo}:{hi}]")
+            for lo, hi in chunk_ranges(n, chunk)
+        ]
+
+    def reduce_subtasks(self, ctx: OpContext, results: List[Any], **inputs: Any) -> Any:
+        X, like, handles = ctx.metadata.pop("_op_pending")
+        try:
+            G = torch.cat(results, dim=0)
+            sel = D.bulyan_select_from_gram(G, self.f)
+            return to_like(D.mean_of_medians(X, 2 * self.f, rows=sel), like)
+        finally:
+            self._cleanup(handles)
+
+
 class GeometricMedian(Aggregator):
     """Weiszfeld fixed point; barriered per-iteration fan-out on CPU pools
     (reference geometric_median.py:106-158), fused kernels on GPU."""

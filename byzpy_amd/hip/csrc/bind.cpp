@@ -4,6 +4,7 @@
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 
+#include <climits>
 #include <vector>
 
 #include "launchers.h"
@@ -88,8 +89,37 @@ torch::TensorOptions i32_like(const torch::Tensor& X) {
 
 // -- ops --------------------------------------------------------------------
 
-torch::Tensor colsel(torch::Tensor X, int64_t mode, int64_t f) {
+// mean-around-median keeps n - f values, so any f < n is meaningful
+// (Bulyan runs it with 2f >= n); median and trimmed mean need 2f < n
+void check_colsel_f(int64_t mode, int64_t f, int64_t n) {
+  TORCH_CHECK(f >= 0 && (mode == 2 ? f < n : 2 * f < n), "bad f for colsel");
+}
+
+// Row-indexed colsel: the statistic over X[rows] without the gather. Only
+// the selected count m is capped (colsel.hip register / LDS kernels, never
+// the radix engine); the source matrix may have any number of rows.
+torch::Tensor colsel_rows(const torch::Tensor& X, int64_t mode, int64_t f,
+                          const torch::Tensor& rows) {
+  check_i32(rows, 1, "rows");
+  const int64_t m = rows.numel();
+  TORCH_CHECK(m >= 1 && m <= COLSEL_MAX_ROWS, "colsel with rows supports 1 <= ",
+              "len(rows) <= ", COLSEL_MAX_ROWS, ", got ", m);
+  TORCH_CHECK(X.size(0) >= 1 && X.size(0) <= INT_MAX, "bad row count");
+  check_colsel_f(mode, f, m);
+  const long d = (long)X.size(1);
+  auto out = torch::empty({d}, X.options());
+  by_dtype(X, [&](auto tag) {
+    using T = TAG_T(tag);
+    launch_colsel<T>(ptr<T>(X), ptr<T>(out), (int)m, d, (int)mode, (int)f,
+                     i32(rows), (int)X.size(0), cur_stream());
+  });
+  return out;
+}
+
+torch::Tensor colsel(torch::Tensor X, int64_t mode, int64_t f,
+                     c10::optional<torch::Tensor> rows) {
   check_matrix(X);
+  if (rows.has_value()) return colsel_rows(X, mode, f, *rows);
   const int n = (int)X.size(0);
   const long d = (long)X.size(1);
   // measured crossovers: register kernels to n = 64; past that the
@@ -101,13 +131,13 @@ torch::Tensor colsel(torch::Tensor X, int64_t mode, int64_t f) {
       n <= 65535 && (n > 512 || (n > 64 && d >= 32768));
   TORCH_CHECK(n >= 1 && (n <= 512 || radix_ok),
               "colsel supports 1 <= n <= 65535, got ", n);
-  TORCH_CHECK(f >= 0 && 2 * f < n, "bad f for colsel");
+  check_colsel_f(mode, f, n);
   auto out = torch::empty({d}, X.options());
   if (!radix_ok) {
     by_dtype(X, [&](auto tag) {
       using T = TAG_T(tag);
       launch_colsel<T>(ptr<T>(X), ptr<T>(out), n, d, (int)mode, (int)f,
-                       cur_stream());
+                       nullptr, n, cur_stream());
     });
     return out;
   }
@@ -225,9 +255,23 @@ torch::Tensor gram(torch::Tensor X) {
 // Fused Krum selection: Gram -> q winner indices (one kernel, replaces
 // the D2-build + two topk torch chains whose launch overhead caps the
 // d-sharded multi-GPU scaling).
-torch::Tensor krum_select(torch::Tensor G, int64_t f, int64_t q) {
+// iterative = true: the q picks of the Bulyan selection instead (each pick
+// rescored among the rows still alive, then removed), int32 (q,) in pick
+// order; every pick needs k = alive - f - 1 >= 1.
+torch::Tensor krum_select(torch::Tensor G, int64_t f, int64_t q,
+                          bool iterative) {
   check_gram(G, "G");
   const int n = (int)G.size(0);
+  if (iterative) {
+    TORCH_CHECK(n <= KRUM_ITER_MAX_N, "krum_select(iterative) supports n <= ",
+                KRUM_ITER_MAX_N, ", got ", n);
+    TORCH_CHECK(q >= 1 && f >= 0 && n - q - f >= 1,
+                "krum_select(iterative) needs q >= 1, f >= 0, n - q - f >= 1");
+    auto picks = torch::empty({q}, i32_like(G));
+    launch_krum_select_iter(f32(G), n, (int)f, (int)q, i32(picks),
+                            cur_stream());
+    return picks;
+  }
   TORCH_CHECK(n <= 512, "krum_select supports n <= 512");
   TORCH_CHECK(q >= 1 && q <= n && f >= 0 && n - f - 1 >= 1);
   auto idx = torch::empty({q}, i32_like(G));
@@ -473,7 +517,9 @@ torch::Tensor caf_colsum(torch::Tensor X, torch::Tensor a,
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
-  m.def("colsel", &colsel, "columnwise median/trimmed-mean/meamed");
+  m.def("colsel", &colsel, "columnwise median/trimmed-mean/meamed",
+        py::arg("X"), py::arg("mode"), py::arg("f"),
+        py::arg("rows") = c10::nullopt);
   m.def("row_sqnorms", &row_sqnorms);
   m.def("row_center_sqdists", &row_center_sqdists);
   m.def("row_scale", &row_scale);
@@ -481,7 +527,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("group_mean_rows", &group_mean_rows);
   m.def("bucket_mean", &bucket_mean);
   m.def("gram", &gram);
-  m.def("krum_select", &krum_select);
+  m.def("krum_select", &krum_select, py::arg("G"), py::arg("f"), py::arg("q"),
+        py::arg("iterative") = false);
   m.def("caf_matvec", &caf_matvec);
   m.def("caf_colsum", &caf_colsum, py::arg("X"), py::arg("a"),
         py::arg("mu") = c10::nullopt, py::arg("scale") = c10::nullopt);

@@ -43,6 +43,67 @@ DEV int vecify(int x) {
 enum Mode { MEDIAN = 0, TRIMMED = 1, MEAMED = 2 };
 
 // ---------------------------------------------------------------------------
+// Row-indexed variants (template <bool ROWS>): the statistic runs over the
+// rows named by `rows[0..n)` of an (n_src, d) matrix, as if on X[rows],
+// without the gather. ROWS = false is the plain kernel and compiles to the
+// code it had before the variant existed: every use of `rows` sits behind
+// the compile-time flag.
+//
+// A row's offset rows[i] * rowstride is the same for every lane, so the
+// register kernels never compute it per lane: before the column loop lane l
+// of each wave stages the 64-bit BYTE offset of selected row min(l, n-1) in
+// two VGPRs (one coalesced 4 B/lane read of `rows`), and the unrolled load
+// phase pulls offset i into SGPRs with v_readlane (i is compile-time) —
+// two readlanes and one 64-bit pointer add per row, no multiply, no
+// per-lane index load. Slots past n repeat the last row, exactly like the plain walk that
+// stops advancing; the pad logic overwrites them. Indices are clamped to
+// [0, n_src) so a bad `rows` can misselect but never read out of bounds.
+//
+// v_readlane returns lane i's register whatever EXEC says, but the value is
+// only defined if lane i was active when it was written AND the compiler is
+// free to assume nothing about inactive lanes — so the ROWS column loops
+// keep whole waves active (see wave_active) and clamp/predicate the tail
+// lanes instead of dropping them.
+// ---------------------------------------------------------------------------
+
+typedef unsigned int u32;
+
+struct RowOffsets { u32 lo, hi; };
+
+// rowbytes: bytes from one row of X to the next
+DEV RowOffsets stage_row_offsets(const int* __restrict__ rows, int n,
+                                 int n_src, long rowbytes) {
+  const int lane = threadIdx.x & 63;
+  int r = rows[min(lane, n - 1)];
+  r = min(max(r, 0), n_src - 1);
+  const unsigned long off = (unsigned long)r * (unsigned long)rowbytes;
+  return {(u32)off, (u32)(off >> 32)};
+}
+
+// `base` moved to selected row I (compile-time); the byte offset is a
+// wave-uniform scalar pair, so the move is one 64-bit add per lane
+template <int I, typename E>
+DEV const E* at_row(const E* base, const RowOffsets& ro) {
+  const u32 lo = __builtin_amdgcn_readlane(ro.lo, I);
+  const u32 hi = __builtin_amdgcn_readlane(ro.hi, I);
+  // a register pair, not (hi << 32) | lo: the compiler turns the OR of
+  // disjoint halves into two separate 64-bit adds
+  typedef u32 u32x2 __attribute__((ext_vector_type(2)));
+  const u32x2 pair = {lo, hi};
+  const unsigned long off = __builtin_bit_cast(unsigned long, pair);
+  return reinterpret_cast<const E*>(reinterpret_cast<const char*>(base) + off);
+}
+
+// Column-loop condition. Plain kernels run a lane while its own unit is in
+// range; ROWS kernels run the whole wave while its FIRST lane's unit is
+// (tail lanes clamp their loads and skip the store).
+template <bool ROWS>
+DEV bool wave_active(long unit, long nunits) {
+  if (ROWS) return unit - (long)(threadIdx.x & 63) < nunits;
+  return unit < nunits;
+}
+
+// ---------------------------------------------------------------------------
 // register variant, n <= P, P in {8, 16, 32, 64}
 // ---------------------------------------------------------------------------
 
@@ -151,19 +212,36 @@ DEV float extract_at(const float (&v)[P], int pos) {
   return r;
 }
 
+// Indexed load phase shared by the register kernels: element I of `dst`
+// comes from at_row<I>(base). Same pinned load/advance alternation as
+// the plain walk (see the load-phase comment in colsel_reg_kernel).
+template <int P, int I = 0, typename E>
+DEV void load_rows_indexed(E (&dst)[P], const E* base, const RowOffsets& ro) {
+  if constexpr (I < P) {
+    dst[I] = *at_row<I>(base, ro);
+    __builtin_amdgcn_sched_barrier(0);
+    load_rows_indexed<P, I + 1>(dst, base, ro);
+  }
+}
+
 // MEAMED keeps two live P-float arrays (values + deviation keys); at P=64
 // that needs ~140 VGPRs, above the occupancy heuristic's 128 cap — the
 // MEAMED instantiations get __launch_bounds__(256, 2) via this trait so the
 // allocator may use 256 VGPRs instead of spilling, while MEDIAN/TRIMMED
 // keep the default 4-waves/SIMD occupancy.
-template <int P, int MODE, typename T>
+template <int P, int MODE, typename T, bool ROWS>
 __global__ void
-__launch_bounds__(256, (MODE == 2 && P >= 64) ? 2 : 4)
+__launch_bounds__(256, (MODE == 2 && P >= 64)           ? 2
+                       : (ROWS && MODE == 1 && P >= 64) ? 3
+                                                        : 4)
 colsel_reg_kernel(const T* __restrict__ X, T* __restrict__ out,
-                                  int n, long d, int f) {
+                                  int n, long d, int f,
+                                  const int* __restrict__ rows, int n_src) {
   const long col0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long stride = (long)gridDim.x * blockDim.x;
-  for (long col = col0; col < d; col += stride) {
+  RowOffsets ro = {0u, 0u};
+  if (ROWS) ro = stage_row_offsets(rows, n, n_src, d * (long)sizeof(T));
+  for (long col = col0; wave_active<ROWS>(col, d); col += stride) {
     float v[P];
     T raw[P];
     // Load phase. Two rules keep the address walk at ONE live base:
@@ -174,7 +252,11 @@ colsel_reg_kernel(const T* __restrict__ X, T* __restrict__ out,
     //     them through v_writelane/readlane (~1100 VALU per column).
     // Once a load ISSUES its address registers are free; the loads stay
     // in flight and the converts below wait on counted vmcnt.
-    {
+    if (ROWS) {
+      // indexed walk: scalar row offset + this lane's (clamped) column
+      const T* xc = X + min(col, d - 1);
+      load_rows_indexed<P>(raw, xc, ro);
+    } else {
       const T* p = X + col;
 #pragma unroll
       for (int i = 0; i < P; ++i) {
@@ -252,7 +334,7 @@ colsel_reg_kernel(const T* __restrict__ X, T* __restrict__ out,
         if (i < nfv) s += v[i];
       result = s / (float)(n - f);
     }
-    out[col] = from_f<T>(result);
+    if (!ROWS || col < d) out[col] = from_f<T>(result);
   }
 }
 
@@ -264,8 +346,6 @@ colsel_reg_kernel(const T* __restrict__ X, T* __restrict__ out,
 // BOTH columns (no packed f32 min/max exists on gfx950), with half the
 // register footprint (P u32 regs for 2 columns) and 4 B/lane loads.
 // ---------------------------------------------------------------------------
-
-typedef unsigned int u32;
 
 DEV u32 pk_min_u16(u32 a, u32 b) {
   u32 r;
@@ -386,7 +466,7 @@ DEV u32 extract_at_pk(const u32 (&v)[P], int pos) {
 // independent sorting networks; QUADS=false: one pair (4 B/lane).
 // MODE: MEDIAN or TRIMMED (order statistics read straight off the sorted
 // keys; TRIMMED unpacks the kept range and sums in f32).
-template <int P, bool QUADS, int MODE = MEDIAN>
+template <int P, bool QUADS, int MODE, bool ROWS>
 __global__ void
 // QUADS at P=64 holds two 64-u32 arrays (~150 VGPRs): ask for 3 waves/SIMD
 // so the allocator doesn't cap at 128 and spill
@@ -395,21 +475,32 @@ __launch_bounds__(256, (QUADS && P >= 64) ? 3
                                                      : 4)
 colsel_pk_median_bf16(const unsigned short* __restrict__ X,
                                       unsigned short* __restrict__ out, int n,
-                                      long d, int f) {
+                                      long d, int f,
+                                      const int* __restrict__ rows,
+                                      int n_src) {
   const long npairs = d >> 1;
   const long nunits = QUADS ? (npairs >> 1) : npairs;
   const long unit0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long stride = (long)gridDim.x * blockDim.x;
   const long rowstride = d >> 1;  // in u32 units
-  for (long unit = unit0; unit < nunits; unit += stride) {
-    const long pair = QUADS ? unit * 2 : unit;
+  RowOffsets ro = {0u, 0u};
+  if (ROWS) ro = stage_row_offsets(rows, n, n_src, rowstride * (long)sizeof(u32));
+  for (long unit = unit0; wave_active<ROWS>(unit, nunits); unit += stride) {
+    // ROWS: tail lanes of the last wave load a clamped (valid) unit and
+    // skip the store
+    const long ldunit = ROWS ? min(unit, nunits - 1) : unit;
+    const long pair = QUADS ? ldunit * 2 : ldunit;
     u32 v[P], v2[QUADS ? P : 1];
     // raw loads first + pinned alternation: see colsel_reg_kernel's load
     // phase for why (one live base, no SGPR spill storm). The walk
     // condition is vecified too — 64 uniform selects otherwise become
     // batched SGPR mask pairs and spill at QUADS register pressure.
     const u32* p = reinterpret_cast<const u32*>(X) + pair;
-    if (n == P) {
+    if (ROWS) {
+      // indexed walk (pairs only: QUADS is an un-indexed A/B aid)
+      static_assert(!(ROWS && QUADS), "no indexed QUADS variant");
+      load_rows_indexed<P>(v, p, ro);
+    } else if (n == P) {
       // full tile (the flagship n=64 shape): unconditional walk, no pads
       // — drops ~190 predication VALU ops from a VALU-bound kernel
 #pragma unroll
@@ -584,7 +675,7 @@ colsel_pk_median_bf16(const unsigned short* __restrict__ X,
       c1.h = __float2bfloat16(m1);
       o.s[0] = c0.s;
       o.s[1] = c1.s;
-      outw[pair + half] = o.w;
+      if (!ROWS || unit < nunits) outw[pair + half] = o.w;
     }
   }
 }
@@ -609,10 +700,11 @@ constexpr int LDS_COLS = 64;
 // P=512: 128 KB -> 1 block)
 constexpr int LDS_THREADS = 512;
 
-template <int MODE, typename T>
+template <int MODE, typename T, bool ROWS>
 __global__ void __launch_bounds__(LDS_THREADS)
 colsel_lds_kernel(const T* __restrict__ X, T* __restrict__ out,
-                  int n, long d, int f, int P) {
+                  int n, long d, int f, int P,
+                  const int* __restrict__ rows, int n_src) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* buf = reinterpret_cast<float*>(smem);  // [P][LDS_COLS]
   const int t = threadIdx.x;
@@ -624,8 +716,17 @@ colsel_lds_kernel(const T* __restrict__ X, T* __restrict__ out,
     const int row = idx / LDS_COLS;
     const int c = idx % LDS_COLS;
     float v = PAD;
-    if (row < n && c < cols)
-      v = to_f<T>(X[(long)row * d + col0 + c]);
+    if (row < n && c < cols) {
+      int src = row;
+      if (ROWS) {
+        // the 64 idx of one wave iteration share `row` (LDS_COLS == 64):
+        // readfirstlane makes that provable, so rows[row] is one scalar
+        // load per wave and the row offset stays in SGPRs
+        const int r = rows[__builtin_amdgcn_readfirstlane(row)];
+        src = min(max(r, 0), n_src - 1);
+      }
+      v = to_f<T>(X[(long)src * d + col0 + c]);
+    }
     buf[idx] = v;
   }
   __syncthreads();
@@ -702,6 +803,14 @@ inline void by_reg_width(int n, F&& fn) {
   else fn(std::integral_constant<int, 64>{});
 }
 
+// plain (rows == nullptr) or row-indexed kernel variant:
+// fn receives std::bool_constant<ROWS>
+template <typename F>
+inline void by_rows(const int* rows, F&& fn) {
+  if (rows != nullptr) fn(std::true_type{});
+  else fn(std::false_type{});
+}
+
 // grid-stride launch width: one unit per thread, capped at 8192 blocks
 inline int capped_grid(long units, int block) {
   const long want = (units + block - 1) / block;
@@ -716,39 +825,46 @@ inline int capped_grid(long units, int block) {
 
 template <typename T>
 static void colsel_generic(const T* X, T* out, int n, long d, int mode, int f,
-                           hipStream_t stream) {
+                           const int* rows, int n_src, hipStream_t stream) {
   by_mode(mode, [&](auto m) {
     constexpr int MODE = decltype(m)::value;
-    if (n <= 64) {
-      const int block = 256;
-      const int grid = capped_grid(d, block);
-      by_reg_width(n, [&](auto p) {
-        hipLaunchKernelGGL((colsel_reg_kernel<decltype(p)::value, MODE, T>),
-                           dim3(grid), dim3(block), 0, stream, X, out, n, d,
-                           f);
-      });
-    } else {
-      int P = 128;
-      while (P < n) P <<= 1;  // 128/256/512
-      const long grid = (d + LDS_COLS - 1) / LDS_COLS;
-      const size_t lds = (size_t)P * LDS_COLS * sizeof(float);
-      hipLaunchKernelGGL((colsel_lds_kernel<MODE, T>), dim3(grid),
-                         dim3(LDS_THREADS), lds, stream, X, out, n, d, f, P);
-    }
+    by_rows(rows, [&](auto r) {
+      constexpr bool ROWS = decltype(r)::value;
+      if (n <= 64) {
+        const int block = 256;
+        const int grid = capped_grid(d, block);
+        by_reg_width(n, [&](auto p) {
+          hipLaunchKernelGGL(
+              (colsel_reg_kernel<decltype(p)::value, MODE, T, ROWS>),
+              dim3(grid), dim3(block), 0, stream, X, out, n, d, f, rows,
+              n_src);
+        });
+      } else {
+        int P = 128;
+        while (P < n) P <<= 1;  // 128/256/512
+        const long grid = (d + LDS_COLS - 1) / LDS_COLS;
+        const size_t lds = (size_t)P * LDS_COLS * sizeof(float);
+        hipLaunchKernelGGL((colsel_lds_kernel<MODE, T, ROWS>), dim3(grid),
+                           dim3(LDS_THREADS), lds, stream, X, out, n, d, f, P,
+                           rows, n_src);
+      }
+    });
   });
 }
 
 template <>
 void launch_colsel<float>(const float* X, float* out, int n, long d, int mode,
-                          int f, hipStream_t stream) {
-  colsel_generic(X, out, n, d, mode, f, stream);
+                          int f, const int* rows, int n_src,
+                          hipStream_t stream) {
+  colsel_generic(X, out, n, d, mode, f, rows, n_src, stream);
 }
 
 // bf16 with n <= 64 and even d takes the packed path (two columns per lane)
 template <>
 void launch_colsel<__hip_bfloat16>(const __hip_bfloat16* X,
                                    __hip_bfloat16* out, int n, long d,
-                                   int mode, int f, hipStream_t stream) {
+                                   int mode, int f, const int* rows,
+                                   int n_src, hipStream_t stream) {
   if (n <= 64 && (d % 2) == 0) {
     const int block = 256;
     // A/B'd on MI355X: QUADS (8 B/lane) TIED the old full-sort variant
@@ -761,11 +877,12 @@ void launch_colsel<__hip_bfloat16>(const __hip_bfloat16* X,
     unsigned short* Ou = reinterpret_cast<unsigned short*>(out);
     // A/B aid: BYZPY_PK_QUADS=1 re-measures the 4-column (8 B/lane)
     // MEDIAN variant (tied pre-selection-network; see the comment above)
-    if (mode == MEDIAN && n > 32 && (d % 4) == 0 &&
+    if (rows == nullptr && mode == MEDIAN && n > 32 && (d % 4) == 0 &&
         std::getenv("BYZPY_PK_QUADS") != nullptr) {
       const int qgrid = capped_grid(d >> 2, block);
-      hipLaunchKernelGGL((colsel_pk_median_bf16<64, true, MEDIAN>),
-                         dim3(qgrid), dim3(block), 0, stream, Xu, Ou, n, d, f);
+      hipLaunchKernelGGL((colsel_pk_median_bf16<64, true, MEDIAN, false>),
+                         dim3(qgrid), dim3(block), 0, stream, Xu, Ou, n, d, f,
+                         rows, n_src);
       return;
     }
     by_mode(mode, [&](auto m) {
@@ -773,13 +890,17 @@ void launch_colsel<__hip_bfloat16>(const __hip_bfloat16* X,
       // MEAMED stages a 2(f+1)-key strip per thread in LDS (odd stride)
       const size_t lds =
           MODE == MEAMED ? (size_t)block * (2 * (f + 1) + 1) * sizeof(u32) : 0;
-      by_reg_width(n, [&](auto p) {
-        hipLaunchKernelGGL(
-            (colsel_pk_median_bf16<decltype(p)::value, false, MODE>),
-            dim3(grid), dim3(block), lds, stream, Xu, Ou, n, d, f);
+      by_rows(rows, [&](auto r) {
+        constexpr bool ROWS = decltype(r)::value;
+        by_reg_width(n, [&](auto p) {
+          hipLaunchKernelGGL(
+              (colsel_pk_median_bf16<decltype(p)::value, false, MODE, ROWS>),
+              dim3(grid), dim3(block), lds, stream, Xu, Ou, n, d, f, rows,
+              n_src);
+        });
       });
     });
     return;
   }
-  colsel_generic(X, out, n, d, mode, f, stream);
+  colsel_generic(X, out, n, d, mode, f, rows, n_src, stream);
 }

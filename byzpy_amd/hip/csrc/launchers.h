@@ -21,10 +21,16 @@ constexpr int MAX_N_LDS = 1024;
   template decltype(f<__hip_bfloat16>) f<__hip_bfloat16>;
 
 // colsel.hip: register / LDS-sort column selection, n <= 512.
-// mode: 0 median, 1 trimmed mean, 2 mean-around-median
+// mode: 0 median, 1 trimmed mean, 2 mean-around-median.
+// `rows` null: the statistic runs over rows 0..n-1 of the (n, d) matrix.
+// `rows` non-null: an int32 device vector of n distinct row indices into an
+// (n_src, d) matrix; the statistic runs over exactly those rows, as if on
+// X[rows], with no gather (n <= COLSEL_MAX_ROWS counts the selected rows,
+// n_src is unbounded; indices are clamped to [0, n_src)).
+constexpr int COLSEL_MAX_ROWS = 512;
 template <typename T>
 void launch_colsel(const T* X, T* out, int n, long d, int mode, int f,
-                   hipStream_t stream);
+                   const int* rows, int n_src, hipStream_t stream);
 
 // rsel.hip: streaming radix-select engine for large n, same modes.
 // `state` is caller-zeroed d*4 u32 scratch; `med` is a d-float scratch,
@@ -87,6 +93,14 @@ void launch_gaussian_fill(T* out, long d, unsigned long long seed, float mu,
 // krumsel.hip / subsets.hip (K11): f32 Gram / distance matrices only
 void launch_krum_select(const float* G, int n, int f, int q, int* out_idx,
                         float* out_scores, hipStream_t stream);
+// Iterative (Bulyan) selection: q picks in one launch, each the best Krum
+// score among the rows still alive (k = alive - f - 1 nearest alive rows),
+// the pick then leaves the pool; out_idx holds the picks in order. Needs
+// n - q - f >= 1. The per-row sorted distance lists live in LDS, which
+// caps n at KRUM_ITER_MAX_N.
+constexpr int KRUM_ITER_MAX_N = 128;
+void launch_krum_select_iter(const float* G, int n, int f, int q,
+                             int* out_idx, hipStream_t stream);
 void launch_smea_select(const float* G, const int* combos, int n, int m, int C,
                         unsigned long long* best, hipStream_t stream);
 void launch_mda_pass1(const float* D2, const int* prefixes, int P, int n,

@@ -33,19 +33,54 @@ def _gpu(X: torch.Tensor) -> bool:
 # -- coordinate-wise (K1-K3) ------------------------------------------------
 
 
-def median(X: torch.Tensor) -> torch.Tensor:
+# Row-indexed colsel (`rows=`): the statistic over X[rows] with no (m, d)
+# gather. The binding serves it from colsel.hip only (register kernels to
+# m = 64, LDS sort to m = 512), never from the radix engine.
+COLSEL_ROWS_MAX_M = 512
+_COLSEL_RADIX_MIN_D = 32768
+
+
+def _colsel_rows(X: torch.Tensor, mode: int, f: int, rows: torch.Tensor):
+    """Device `rows=` routing. The indexed kernel runs exactly where the
+    un-indexed call on X[rows] would stay in colsel.hip too: m <= 64, or
+    m <= 512 at d < 32768. Larger m at large d gathers and takes the
+    un-indexed op, so the radix engine (rsel.hip) keeps serving it — the
+    LDS sort loses to it there by more than the gather costs."""
+    m, d = int(rows.numel()), X.shape[1]
+    if m <= 64 or (m <= COLSEL_ROWS_MAX_M and d < _COLSEL_RADIX_MIN_D):
+        rows32 = rows.to(device=X.device, dtype=torch.int32).contiguous()
+        return _hip.require().colsel(X.contiguous(), mode, int(f), rows32)
+    return None
+
+
+def median(X: torch.Tensor, rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``rows`` (m distinct row indices) restricts the statistic to those
+    rows, as if on X[rows]; same for trimmed_mean and mean_of_medians."""
+    if rows is not None:
+        out = _colsel_rows(X, _COLSEL_MEDIAN, 0, rows) if _gpu(X) else None
+        return out if out is not None else median(X[rows.long()])
     if _gpu(X) and X.shape[0] <= COLSEL_MAX_N:
         return _hip.require().colsel(X.contiguous(), _COLSEL_MEDIAN, 0)
     return F.median(X)
 
 
-def trimmed_mean(X: torch.Tensor, f: int) -> torch.Tensor:
+def trimmed_mean(
+    X: torch.Tensor, f: int, rows: Optional[torch.Tensor] = None
+) -> torch.Tensor:
+    if rows is not None:
+        out = _colsel_rows(X, _COLSEL_TRIMMED, f, rows) if _gpu(X) else None
+        return out if out is not None else trimmed_mean(X[rows.long()], f)
     if _gpu(X) and X.shape[0] <= COLSEL_MAX_N:
         return _hip.require().colsel(X.contiguous(), _COLSEL_TRIMMED, int(f))
     return F.trimmed_mean(X, f)
 
 
-def mean_of_medians(X: torch.Tensor, f: int) -> torch.Tensor:
+def mean_of_medians(
+    X: torch.Tensor, f: int, rows: Optional[torch.Tensor] = None
+) -> torch.Tensor:
+    if rows is not None:
+        out = _colsel_rows(X, _COLSEL_MEAMED, f, rows) if _gpu(X) else None
+        return out if out is not None else mean_of_medians(X[rows.long()], f)
     if _gpu(X) and X.shape[0] <= COLSEL_MAX_N:
         return _hip.require().colsel(X.contiguous(), _COLSEL_MEAMED, int(f))
     return F.mean_of_medians(X, f)
@@ -106,6 +141,61 @@ def krum_winners_from_gram(G: torch.Tensor, f: int, q: int) -> torch.Tensor:
     return torch.topk(scores, k=q, largest=False).indices.to(torch.int32)
 
 
+# Row cap of krum_select(iterative=True): the kernel keeps every sorted
+# distance row in LDS (KRUM_ITER_MAX_N in csrc/launchers.h).
+BULYAN_SELECT_MAX_N = 128
+
+
+def _check_bulyan(n: int, f: int) -> None:
+    if f < 0 or n < 4 * f + 3:
+        raise ValueError(f"Bulyan needs n >= 4f + 3, got n={n}, f={f}")
+
+
+def bulyan_select_from_gram(G: torch.Tensor, f: int) -> torch.Tensor:
+    """int32 (n - 2f,) Bulyan selection in pick order: n - 2f rounds of
+    Krum among the rows still alive (score = sum of the alive - f - 1
+    smallest squared distances to other alive rows; ties to the smallest
+    index; non-finite distances count as +inf), each winner leaving the
+    pool. One fused launch on device up to BULYAN_SELECT_MAX_N rows; past
+    it, and on CPU, the same picks as sync-free torch ops on the Gram."""
+    n = G.shape[0]
+    _check_bulyan(n, f)
+    theta = n - 2 * f
+    if f == 0:
+        return torch.arange(n, device=G.device, dtype=torch.int32)
+    if _gpu(G) and n <= BULYAN_SELECT_MAX_N:
+        return _hip.require().krum_select(G, int(f), int(theta), True)
+    return _bulyan_select_torch(G, f)
+
+
+def _bulyan_select_torch(G: torch.Tensor, f: int) -> torch.Tensor:
+    """The Bulyan picks as torch ops on the Gram, any device, no host
+    sync: about ten small launches per pick."""
+    n = G.shape[0]
+    theta = n - 2 * f
+    inf = float("inf")
+    D2 = sq_dists_from_gram(G)
+    D2 = torch.where(torch.isfinite(D2), D2, torch.full_like(D2, inf))
+    D2.fill_diagonal_(inf)
+    alive = torch.ones(n, dtype=torch.bool, device=G.device)
+    picks = torch.empty(theta, dtype=torch.int64, device=G.device)
+    for p in range(theta):
+        k = n - p - f - 1
+        # dead columns cost +inf: with k <= alive - 1 they never enter a
+        # k-smallest sum ahead of a finite alive distance
+        near = torch.topk(
+            D2.masked_fill(~alive[None, :], inf), k=k, dim=1, largest=False
+        ).values
+        scores = near.sum(dim=1).masked_fill_(~alive, inf)
+        # first alive row at the minimum (argmin alone could name a dead
+        # row when every alive score is +inf)
+        hit = alive & (scores == scores.min())
+        i = torch.argmax(hit.to(torch.int32))
+        picks[p] = i
+        alive[i] = False
+    return picks.to(torch.int32)
+
+
 def nearest_rows_from_gram(G: torch.Tensor, k: int) -> torch.Tensor:
     """Per row, the indices of its k nearest rows (itself included)."""
     return torch.topk(sq_dists_from_gram(G), k=k, dim=-1, largest=False).indices
@@ -138,6 +228,20 @@ def krum(X: torch.Tensor, f: int) -> torch.Tensor:
         return X[idx.long()[0]].clone()
     scores = multi_krum_scores(X, f)
     return X[int(torch.argmin(scores))].clone()
+
+
+def bulyan(X: torch.Tensor, f: int) -> torch.Tensor:
+    """Bulyan (El Mhamdi et al. 2018): Gram -> n - 2f rows by iterated Krum
+    -> per coordinate the mean of the n - 4f selected values closest to
+    their median. On device: MFMA Gram, one selection launch, one indexed
+    mean-around-median launch reading the selected rows in place — no
+    (theta, d) gather and no host sync."""
+    n = X.shape[0]
+    _check_bulyan(n, f)
+    if f == 0:
+        return mean_of_medians(X, 0)
+    sel = bulyan_select_from_gram(gram(X), f)
+    return mean_of_medians(X, 2 * f, rows=sel)
 
 
 def mean_rows(X: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:

@@ -118,6 +118,59 @@ def krum(X: torch.Tensor, f: int) -> torch.Tensor:
     return X[int(torch.argmin(scores))].clone()
 
 
+def bulyan_select_from_gram(G: torch.Tensor, f: int) -> torch.Tensor:
+    """Bulyan's selection phase (El Mhamdi et al. 2018) on an (n, n) Gram:
+    theta = n - 2f picks; each pick is the surviving row with the smallest
+    Krum score among the survivors (sum of its r - f - 1 smallest squared
+    distances to other survivors, r = survivors left; ties to the smallest
+    index), which then leaves the pool. Returns the picks in order (int64).
+
+    Written row by row in f64 straight from the definition — this is the
+    oracle, deliberately not the vectorised text of hip/dispatch.py."""
+    n = G.shape[0]
+    if f < 0 or n < 4 * f + 3:
+        raise ValueError(f"Bulyan needs n >= 4f + 3, got n={n}, f={f}")
+    if f == 0:
+        return torch.arange(n, dtype=torch.int64)
+    Gd = G.detach().double().cpu()
+    inf = float("inf")
+    D2 = [[inf] * n for _ in range(n)]
+    for i in range(n):
+        for j in range(n):
+            if i == j:
+                continue
+            v = float(Gd[i, i] + Gd[j, j] - 2.0 * Gd[i, j])
+            D2[i][j] = max(v, 0.0) if math.isfinite(v) else inf
+    alive = list(range(n))
+    picks: List[int] = []
+    for _ in range(n - 2 * f):
+        k = len(alive) - f - 1
+        best_i, best_s = -1, inf
+        for i in alive:
+            nearest = sorted(D2[i][j] for j in alive if j != i)[:k]
+            s = math.fsum(nearest) if math.isfinite(nearest[-1]) else inf
+            if best_i < 0 or s < best_s:
+                best_i, best_s = i, s
+        picks.append(best_i)
+        alive.remove(best_i)
+    return torch.tensor(picks, dtype=torch.int64)
+
+
+def bulyan_select(X: torch.Tensor, f: int) -> torch.Tensor:
+    """Bulyan's selected rows, in pick order, from the f32-accumulated Gram
+    of X (see bulyan_select_from_gram)."""
+    Xf = X.float()
+    return bulyan_select_from_gram(Xf @ Xf.T, f)
+
+
+def bulyan(X: torch.Tensor, f: int) -> torch.Tensor:
+    """Bulyan: theta = n - 2f rows chosen by iterated Krum, then per
+    coordinate the mean of the beta = theta - 2f selected values closest to
+    their median."""
+    sel = bulyan_select(X, f).to(X.device)
+    return mean_of_medians(X[sel], 2 * f)
+
+
 def geometric_median(
     X: torch.Tensor,
     *,

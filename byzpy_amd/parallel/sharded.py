@@ -60,6 +60,15 @@ def multi_krum(X_local: torch.Tensor, f: int, q: int) -> torch.Tensor:
     return D.mean_rows(X_local, winners)
 
 
+def bulyan(X_local: torch.Tensor, f: int) -> torch.Tensor:
+    """Bulyan on a d-shard: one (n, n) all-reduce, then the selection —
+    identical on every rank for the same reason as the Krum winners in
+    median_and_multi_krum — and the column step over the selected rows of
+    the local shard. No other communication."""
+    sel = D.bulyan_select_from_gram(_global_gram(X_local), f)
+    return D.mean_of_medians(X_local, 2 * f, rows=sel)
+
+
 def krum(X_local: torch.Tensor, f: int) -> torch.Tensor:
     scores = D.krum_scores_from_gram(_global_gram(X_local), f)
     return X_local[int(torch.argmin(scores))].clone()
