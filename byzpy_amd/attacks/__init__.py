@@ -6,6 +6,8 @@ from byzpy_amd.attacks.ops import (
     LabelFlipAttack,
     LittleAttack,
     MimicAttack,
+    MinMaxAttack,
+    MinSumAttack,
     SignFlipAttack,
 )
 
@@ -18,4 +20,6 @@ __all__ = [
     "GaussianAttack",
     "InfAttack",
     "MimicAttack",
+    "MinMaxAttack",
+    "MinSumAttack",
 ]

@@ -3,7 +3,8 @@
 Reference parity: attacks/{empire,sign_flip,label_flip,little,gaussian,
 inf,mimic}.py. All are cheap elementwise/reduction math; on GPU they run
 as device torch ops over the resident honest-gradient matrix (single
-launches — no fan-out needed).
+launches — no fan-out needed). Min-Max and Min-Sum have no
+reference counterpart.
 """
 from __future__ import annotations
 
@@ -67,6 +68,41 @@ class LittleAttack(Attack):
     def apply(self, *, honest_grads: Any) -> Any:
         X, like = self._stack(honest_grads)
         return to_like(D.little(X, self.f, self.N), like)
+
+
+class _CloudBoundAttack(Attack):
+    """mu + gamma * p with the largest gamma that keeps the vector inside the
+    honest cloud (Shejwalkar & Houmansadr 2021); subclasses name the bound.
+    ``perturbation``: "unit" (-mu/||mu||), "std" (-sigma, the paper's
+    default) or "sign" (-sign(mu))."""
+
+    uses_honest_grads = True
+    _op = None  # dispatch function (X, perturbation) -> (d,)
+
+    def __init__(self, perturbation: str = "std", *, chunk_size: int = 8192) -> None:
+        D._perturb_code(perturbation)  # ValueError on an unknown name
+        self.perturbation = perturbation
+        self.chunk_size = int(chunk_size)
+
+    def apply(self, *, honest_grads: Any) -> Any:
+        X, like = self._stack(honest_grads)
+        return to_like(type(self)._op(X, self.perturbation), like)
+
+
+class MinMaxAttack(_CloudBoundAttack):
+    """Min-Max: max_i ||m - x_i|| stays within the largest honest pairwise
+    distance."""
+
+    name = "attack/min-max"
+    _op = staticmethod(D.min_max)
+
+
+class MinSumAttack(_CloudBoundAttack):
+    """Min-Sum: sum_i ||m - x_i||^2 stays within the largest such sum of an
+    honest row."""
+
+    name = "attack/min-sum"
+    _op = staticmethod(D.min_sum)
 
 
 class GaussianAttack(Attack):

@@ -376,6 +376,30 @@ torch::Tensor little_fused(torch::Tensor X, double z) {
   return out;
 }
 
+// little_fused(X, z, perturb): the statistics pass of the Min-Max / Min-Sum
+// attacks instead. perturb: 0 unit, 1 std, 2 sign; z is unused. Returns
+// (mu, p, stats), all f32: the column mean, the perturbation direction and
+// stats = [a_0..a_{n-1}, b_0..b_{n-1}, c] (launchers.h).
+std::vector<torch::Tensor> little_fused_stats(torch::Tensor X, double /*z*/,
+                                              int64_t perturb) {
+  check_matrix(X);
+  const int64_t n = X.size(0);
+  const long d = (long)X.size(1);
+  TORCH_CHECK(n >= 1, "little_fused(perturb) needs at least one row");
+  check_rows_fit_lds(n, "little_fused(perturb)");
+  TORCH_CHECK(perturb >= 0 && perturb <= 2,
+              "perturb: expected 0 (unit), 1 (std) or 2 (sign), got ", perturb);
+  auto mu = torch::empty({d}, f32_like(X));
+  auto p = torch::empty({d}, f32_like(X));
+  auto stats = torch::zeros({2 * n + 1}, f32_like(X));
+  by_dtype(X, [&](auto tag) {
+    using T = TAG_T(tag);
+    launch_attack_stats<T>(ptr<T>(X), f32(mu), f32(p), f32(stats), (int)n, d,
+                           (int)perturb, cur_stream());
+  });
+  return {mu, p, stats};
+}
+
 // Philox4x32-10 + Box-Muller N(mu, sigma^2) fill (no torch RNG).
 torch::Tensor gaussian_fill(int64_t d, int64_t seed, double mu, double sigma,
                             torch::Tensor like) {
@@ -541,6 +565,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mda_search", &mda_search, "exact min-diameter subset (host DFS)");
   m.def("smea_select", &smea_select, "device SMEA subset selection (K11)");
   m.def("little_fused", &little_fused, "fused Little attack (K14)");
+  m.def("little_fused", &little_fused_stats,
+        "Min-Max / Min-Sum statistics pass (K14): (mu, p, stats)",
+        py::arg("X"), py::arg("z"), py::arg("perturb"));
   m.def("gaussian_fill", &gaussian_fill, "philox gaussian fill (K14)");
   m.def("mda_select", &mda_select, "device MDA two-pass B&B search (K11)",
         py::arg("D2"), py::arg("f"), py::arg("ub") = c10::nullopt);

@@ -86,6 +86,17 @@ void launch_caf_colsum(const T* X, const float* a, const float* mu,
 template <typename T>
 void launch_little(const T* X, T* out, int n, long d, float z,
                    hipStream_t stream);
+// Min-Max / Min-Sum statistics. perturb: 0 unit (p = -mu, unnormalised),
+// 1 std (p = -sigma, population), 2 sign (p = -sign(mu)). Writes the f32
+// d-vectors mu and p and ADDS into the caller-zeroed 2n + 1 floats
+// stats = [a_0..a_{n-1}, b_0..b_{n-1}, c] with a_i = ||mu - x_i||^2,
+// b_i = p . (mu - x_i), c = ||p||^2. n <= 64 is one fused pass; larger n is
+// a moments pass plus row_center_sqdists and caf_matvec, n <= MAX_N_LDS
+// (its sigma is sqrt(sum x^2 / n - mu^2), the fused pass's the root mean
+// squared deviation: they differ where |mu| >> sigma cancels in f32).
+template <typename T>
+void launch_attack_stats(const T* X, float* mu, float* p, float* stats, int n,
+                         long d, int perturb, hipStream_t stream);
 template <typename T>
 void launch_gaussian_fill(T* out, long d, unsigned long long seed, float mu,
                           float sigma, hipStream_t stream);

@@ -542,6 +542,93 @@ def gaussian_attack(
                                         float(sigma), like)
 
 
+# Min-Max / Min-Sum (Shejwalkar & Houmansadr 2021): m = mu + gamma * p with
+# the largest gamma >= 0 that keeps m inside the honest cloud. With
+#   a_i = ||mu - x_i||^2,  b_i = p . (mu - x_i),  c = ||p||^2
+# the distance ||m - x_i||^2 = a_i + 2 gamma b_i + gamma^2 c is a quadratic in
+# gamma, so the optimum is a root, not a search: the formulas below are torch
+# ops on the O(n) statistics, any device and dtype, no host sync.
+# ops/functional.py keeps its own text (explicit differences, bisection).
+
+_PERTURB_CODES = {"unit": 0, "std": 1, "sign": 2}
+
+# Row cap of little_fused(X, z, perturb) (MAX_N_LDS in csrc/launchers.h).
+ATTACK_STATS_MAX_N = 1024
+
+
+def _perturb_code(perturbation: str) -> int:
+    if perturbation not in _PERTURB_CODES:
+        raise ValueError(
+            f"perturbation must be one of {tuple(_PERTURB_CODES)}, "
+            f"got {perturbation!r}"
+        )
+    return _PERTURB_CODES[perturbation]
+
+
+def min_max_gamma(
+    a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, tau: torch.Tensor
+) -> torch.Tensor:
+    """Largest gamma with max_i (a_i + 2 gamma b_i + gamma^2 c) <= tau.
+    Row i allows [0, gamma_i], gamma_i = (-b_i + sqrt(b_i^2 + c D_i)) / c
+    with D_i = max(tau - a_i, 0); for b_i >= 0 that difference cancels, so
+    it is evaluated as D_i / (b_i + sqrt(b_i^2 + c D_i)). c = 0 gives 0."""
+    delta = (tau - a).clamp_min(0.0)
+    root = torch.sqrt(b * b + c * delta)
+    den = b + root
+    one = torch.ones_like(den)
+    pos = delta / torch.where(den > 0, den, one)  # den = 0 only if delta = 0
+    neg = (root - b) / torch.where(c > 0, c, torch.ones_like(c))
+    gamma = torch.where(b >= 0, pos, neg).min()
+    return torch.where(c > 0, gamma, torch.zeros_like(gamma))
+
+
+def min_sum_gamma(a: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
+    """Largest gamma with sum_i (a_i + 2 gamma b_i + gamma^2 c) <= tau_s.
+    sum_i b_i = 0 and sum_j ||x_i - x_j||^2 = n a_i + sum_j a_j, so the
+    constraint is n gamma^2 c <= n max_i a_i. c = 0 gives 0."""
+    gamma = torch.sqrt(a.max() / torch.where(c > 0, c, torch.ones_like(c)))
+    return torch.where(c > 0, gamma, torch.zeros_like(gamma))
+
+
+def attack_stats(X: torch.Tensor, perturbation: str = "std"):
+    """(mu, p, a, b, c) of a device matrix, f32: one fused pass to n = 64,
+    three kernels to n = 1024. "unit" returns the unnormalised p = -mu (m
+    does not change when p is rescaled)."""
+    n = X.shape[0]
+    mu, p, stats = _hip.require().little_fused(
+        X.contiguous(), 0.0, _perturb_code(perturbation)
+    )
+    return mu, p, stats[:n], stats[n : 2 * n], stats[2 * n]
+
+
+def _attack_device(X: torch.Tensor) -> bool:
+    return _gpu(X) and 1 <= X.shape[0] <= ATTACK_STATS_MAX_N
+
+
+def min_max(X: torch.Tensor, perturbation: str = "std") -> torch.Tensor:
+    """Min-Max attack: the farthest m = mu + gamma p whose largest distance to
+    an honest row stays within the largest honest pairwise distance. On
+    device: the statistics pass, the MFMA Gram for tau, gamma as a device
+    scalar — no host sync, capturable into a hipGraph."""
+    _perturb_code(perturbation)
+    if not _attack_device(X):
+        return F.min_max(X, perturbation)
+    mu, p, a, b, c = attack_stats(X, perturbation)
+    tau = sq_dists_from_gram(gram(X)).max()
+    return torch.addcmul(mu, min_max_gamma(a, b, c, tau), p).to(X.dtype)
+
+
+def min_sum(X: torch.Tensor, perturbation: str = "std") -> torch.Tensor:
+    """Min-Sum attack: the farthest m = mu + gamma p whose summed squared
+    distance to the honest rows stays within the largest such sum of an
+    honest row. Needs no Gram: gamma = sqrt(max_i a_i / c)."""
+    _perturb_code(perturbation)
+    if not _attack_device(X):
+        return F.min_sum(X, perturbation)
+    mu, p, a, _, c = attack_stats(X, perturbation)
+    return torch.addcmul(mu, min_sum_gamma(a, c), p).to(X.dtype)
+
+
 # -- remaining ops: torch composition on either device ----------------------
 
 

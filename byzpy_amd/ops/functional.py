@@ -552,3 +552,110 @@ def inf_attack(like: torch.Tensor) -> torch.Tensor:
 
 def mimic(honest: torch.Tensor, epsilon: int = 0) -> torch.Tensor:
     return honest[epsilon].clone()
+
+
+# Min-Max / Min-Sum (Shejwalkar & Houmansadr, NDSS 2021): m = mu + gamma * p
+# with the largest gamma >= 0 that keeps m inside the honest cloud. This is
+# the oracle's own text: explicit differences, explicit pairwise distances
+# and gamma by bisection on the constraint, all in f64. The device path
+# (hip/dispatch.py) uses a fused statistics pass and the closed-form root.
+
+PERTURBATIONS = ("unit", "std", "sign")
+
+
+def attack_perturbation(honest: torch.Tensor, perturbation: str = "std"):
+    """(mu, p) in f64: the column mean and the perturbation direction,
+    "unit" -mu/||mu||, "std" -sigma (population), "sign" -sign(mu)."""
+    if perturbation not in PERTURBATIONS:
+        raise ValueError(
+            f"perturbation must be one of {PERTURBATIONS}, got {perturbation!r}"
+        )
+    H = honest.double()
+    mu = H.mean(dim=0)
+    if perturbation == "unit":
+        norm = mu.norm()
+        p = -mu / norm if float(norm) > 0.0 else torch.zeros_like(mu)
+    elif perturbation == "std":
+        p = -H.std(dim=0, unbiased=False)
+    else:
+        p = -torch.sign(mu)
+    return mu, p
+
+
+def _largest_feasible(feasible) -> float:
+    """Largest gamma >= 0 with feasible(gamma), for a constraint that holds
+    on an interval [0, gamma*]: bracket [hi/2, hi] by doubling (or halving)
+    from 1, then 64 bisection steps."""
+    if not feasible(0.0):
+        return 0.0
+    hi = 1.0
+    if feasible(hi):
+        while feasible(hi):
+            hi *= 2.0
+            if hi > 1e300:
+                raise ValueError("constraint never binds")
+    else:
+        while not feasible(0.5 * hi):
+            hi *= 0.5
+            if hi < 1e-300:
+                return 0.0
+    lo = 0.5 * hi
+    for _ in range(64):
+        mid = 0.5 * (lo + hi)
+        if feasible(mid):
+            lo = mid
+        else:
+            hi = mid
+    return lo
+
+
+def _attack_terms(honest: torch.Tensor, perturbation: str):
+    """mu, p and the terms of ||mu + gamma p - x_i||^2 = a_i + 2 gamma b_i +
+    gamma^2 c, from explicit differences in f64."""
+    mu, p = attack_perturbation(honest, perturbation)
+    diff = mu[None, :] - honest.double()
+    a = (diff * diff).sum(dim=1)
+    b = (diff * p[None, :]).sum(dim=1)
+    c = float((p * p).sum())
+    return mu, p, a, b, c
+
+
+def _pairwise_sq_dists_explicit(honest: torch.Tensor) -> torch.Tensor:
+    """(n, n) squared distances from explicit differences, f64, a row at a
+    time (no (n, n, d) temporary)."""
+    H = honest.double()
+    return torch.stack([((H - H[i][None, :]) ** 2).sum(dim=1) for i in range(len(H))])
+
+
+def min_max_gamma(honest: torch.Tensor, perturbation: str = "std") -> float:
+    """Largest gamma with max_i ||m - x_i||^2 <= max_ij ||x_i - x_j||^2."""
+    _, _, a, b, c = _attack_terms(honest, perturbation)
+    if c == 0.0:
+        return 0.0
+    tau = float(_pairwise_sq_dists_explicit(honest).max())
+    return _largest_feasible(
+        lambda g: float((a + 2.0 * g * b + g * g * c).max()) <= tau
+    )
+
+
+def min_sum_gamma(honest: torch.Tensor, perturbation: str = "std") -> float:
+    """Largest gamma with sum_i ||m - x_i||^2 <= max_i sum_j ||x_i - x_j||^2."""
+    _, _, a, b, c = _attack_terms(honest, perturbation)
+    if c == 0.0:
+        return 0.0
+    tau_s = float(_pairwise_sq_dists_explicit(honest).sum(dim=1).max())
+    return _largest_feasible(
+        lambda g: float((a + 2.0 * g * b + g * g * c).sum()) <= tau_s
+    )
+
+
+def min_max(honest: torch.Tensor, perturbation: str = "std") -> torch.Tensor:
+    mu, p = attack_perturbation(honest, perturbation)
+    gamma = min_max_gamma(honest, perturbation)
+    return (mu + gamma * p).to(honest.dtype)
+
+
+def min_sum(honest: torch.Tensor, perturbation: str = "std") -> torch.Tensor:
+    mu, p = attack_perturbation(honest, perturbation)
+    gamma = min_sum_gamma(honest, perturbation)
+    return (mu + gamma * p).to(honest.dtype)
