@@ -117,8 +117,47 @@ torch::Tensor colsel_rows(const torch::Tensor& X, int64_t mode, int64_t f,
 }
 
 torch::Tensor colsel(torch::Tensor X, int64_t mode, int64_t f,
-                     c10::optional<torch::Tensor> rows) {
+                     c10::optional<torch::Tensor> rows,
+                     c10::optional<torch::Tensor> gram);
+
+// colsel(X, 0, f, gram=G): the column median, and G overwritten with
+// X X^T. One pass over X where the fused kernel applies (bf16,
+// 32 < n <= 64, even d), else the median and Gram launches one after the
+// other, so the call means the same for every input.
+torch::Tensor colsel_with_gram(const torch::Tensor& X, int64_t mode, int64_t f,
+                               bool has_rows, const torch::Tensor& G) {
+  TORCH_CHECK(mode == 0, "colsel(gram=) computes the median: expected mode 0, ",
+              "got ", mode);
+  TORCH_CHECK(!has_rows, "colsel(gram=) does not take rows");
+  check_gram(G, "gram");
+  const int64_t n = X.size(0);
+  const long d = (long)X.size(1);
+  TORCH_CHECK(G.size(0) == n, "gram: expected (", n, ", ", n, "), got (",
+              G.size(0), ", ", G.size(1), ")");
+  TORCH_CHECK(G.device() == X.device(), "gram: expected X's device");
+  if (X.scalar_type() == torch::kBFloat16 && median_gram_bf16_applies(n, d)) {
+    check_colsel_f(mode, f, n);
+    auto out = torch::empty({d}, X.options());
+    G.zero_();
+    launch_median_gram_bf16(ptr<__hip_bfloat16>(X), ptr<__hip_bfloat16>(out),
+                            f32(G), (int)n, d, cur_stream());
+    return out;
+  }
+  auto out = colsel(X, mode, f, c10::nullopt, c10::nullopt);
+  G.zero_();
+  by_dtype(X, [&](auto tag) {
+    using T = TAG_T(tag);
+    launch_gram<T>(ptr<T>(X), f32(G), (int)n, d, cur_stream());
+  });
+  return out;
+}
+
+torch::Tensor colsel(torch::Tensor X, int64_t mode, int64_t f,
+                     c10::optional<torch::Tensor> rows,
+                     c10::optional<torch::Tensor> gram) {
   check_matrix(X);
+  if (gram.has_value())
+    return colsel_with_gram(X, mode, f, rows.has_value(), *gram);
   if (rows.has_value()) return colsel_rows(X, mode, f, *rows);
   const int n = (int)X.size(0);
   const long d = (long)X.size(1);
@@ -543,7 +582,8 @@ torch::Tensor caf_colsum(torch::Tensor X, torch::Tensor a,
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("colsel", &colsel, "columnwise median/trimmed-mean/meamed",
         py::arg("X"), py::arg("mode"), py::arg("f"),
-        py::arg("rows") = c10::nullopt);
+        py::arg("rows") = c10::nullopt, py::kw_only(),
+        py::arg("gram") = c10::nullopt);
   m.def("row_sqnorms", &row_sqnorms);
   m.def("row_center_sqdists", &row_center_sqdists);
   m.def("row_scale", &row_scale);

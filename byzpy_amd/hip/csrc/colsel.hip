@@ -7,18 +7,21 @@
 //
 // Two variants:
 //  - register kernel (n <= 64): the column lives in a register array; the
-//    bitonic network is fully unrolled so every index is compile-time
+//    sorting network is fully unrolled so every index is compile-time
 //    (guide §5.4 rule 20 — runtime-indexed register arrays spill).
 //    Order statistics at runtime positions are extracted with predicated
 //    unrolled scans for the same reason.
 //  - LDS kernel (64 < n <= 512): one wave per block, each lane owns a
 //    column staged in LDS with a +1 pad row stride (bank-conflict free,
 //    guide §6 G4); runtime bitonic loops.
+// Plus, for bf16 with 32 < n <= 64, the register median fused with the
+// Gram in one pass over X (median_gram_bf16_kernel).
 //
 // Loads are coalesced: adjacent lanes read adjacent columns, so each
 // row-iteration is one 256 B (f32) / 128 B (bf16) wave transaction.
 #include "common.h"
 #include "launchers.h"
+#include "oem_sort.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -180,27 +183,17 @@ DEV void median_select_reg(float (&v)[P], float& mlo, float& mhi) {
   mhi = v[P / 2];
 }
 
-// standalone half-sort (see bitonic_sort_pk_half for why source order
-// matters): UP=true ascending, UP=false the mirrored descending network
+// standalone half-sort (see oem_sort_pk_half for why source order matters
+// and for the network): UP=true ascending, UP=false the mirrored descending
+// network
 template <int P2, bool UP>
-DEV void bitonic_sort_reg_half(float (&v)[P2]) {
-#pragma unroll
-  for (int k = 2; k <= P2; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j > 0; j >>= 1) {
-#pragma unroll
-      for (int i = 0; i < P2; ++i) {
-        const int l = i ^ j;
-        if (l > i) {
-          const bool asc = ((i & k) == 0) == UP;
-          const float a = v[i], b = v[l];
-          const float lo = fminf(a, b), hi = fmaxf(a, b);
-          v[i] = asc ? lo : hi;
-          v[l] = asc ? hi : lo;
-        }
-      }
-    }
-  }
+DEV void oem_sort_reg_half(float (&v)[P2]) {
+  auto ce = [&](int lo, int hi) __attribute__((always_inline)) {
+    const float a = v[lo], b = v[hi];
+    v[lo] = fminf(a, b);
+    v[hi] = fmaxf(a, b);
+  };
+  oem::sort<P2, UP>(ce);
 }
 
 template <int P>
@@ -286,10 +279,10 @@ colsel_reg_kernel(const T* __restrict__ X, T* __restrict__ out,
             if (i >= nv) v[i] = (i < n_lo) ? -PAD : PAD;
         }
         if (h == 0)
-          bitonic_sort_reg_half<P / 2, true>(
+          oem_sort_reg_half<P / 2, true>(
               *reinterpret_cast<float(*)[P / 2]>(&v[0]));
         else
-          bitonic_sort_reg_half<P / 2, false>(
+          oem_sort_reg_half<P / 2, false>(
               *reinterpret_cast<float(*)[P / 2]>(&v[P / 2]));
       }
       float mlo, mhi;
@@ -341,7 +334,7 @@ colsel_reg_kernel(const T* __restrict__ X, T* __restrict__ out,
 // ---------------------------------------------------------------------------
 // Packed bf16 median (n <= 64, even d): TWO adjacent columns per thread.
 // Order statistics only need a monotone key, so bf16 values become
-// sortable u16 keys (sign-flip transform) and the bitonic network runs on
+// sortable u16 keys (sign-flip transform) and the sorting networks run on
 // v_pk_min_u16 / v_pk_max_u16 — one instruction per compare-exchange for
 // BOTH columns (no packed f32 min/max exists on gfx950), with half the
 // register footprint (P u32 regs for 2 columns) and 4 B/lane loads.
@@ -405,29 +398,21 @@ DEV void bitonic_sort_pk(u32 (&v)[P]) {
 
 // standalone half-sort for the median selection path: UP=true ascending,
 // UP=false the mirrored (descending) network. Sorting a half touches only
-// its own P2 registers, so in source order the FIRST half's 240 CEs issue
-// while the second half's row loads are still in flight (the shared
-// <P, P/2> network's k=2 phase touches all P loads up front and forces a
-// full vmcnt(0) wait before any compute).
+// its own P2 registers, so in source order the FIRST half's compare-
+// exchanges issue while the second half's row loads are still in flight
+// (the shared <P, P/2> network's k=2 phase touches all P loads up front and
+// forces a full vmcnt(0) wait before any compute).
+// The schedule is Batcher's odd-even merge sort (oem_sort.h): 191
+// compare-exchanges per 32 keys against the bitonic network's 240 at the
+// same depth — 196 packed ops fewer per column pair on a VALU-bound kernel.
 template <int P2, bool UP>
-DEV void bitonic_sort_pk_half(u32 (&v)[P2]) {
-#pragma unroll
-  for (int k = 2; k <= P2; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j > 0; j >>= 1) {
-#pragma unroll
-      for (int i = 0; i < P2; ++i) {
-        const int l = i ^ j;
-        if (l > i) {
-          const bool asc = ((i & k) == 0) == UP;
-          const u32 a = v[i], b = v[l];
-          const u32 lo = pk_min_u16(a, b), hi = pk_max_u16(a, b);
-          v[i] = asc ? lo : hi;
-          v[l] = asc ? hi : lo;
-        }
-      }
-    }
-  }
+DEV void oem_sort_pk_half(u32 (&v)[P2]) {
+  auto ce = [&](int lo, int hi) __attribute__((always_inline)) {
+    const u32 a = v[lo], b = v[hi];
+    v[lo] = pk_min_u16(a, b);
+    v[hi] = pk_max_u16(a, b);
+  };
+  oem::sort<P2, UP>(ce);
 }
 
 // packed twin of median_select_reg (see its comment): split the bitonic
@@ -535,7 +520,7 @@ colsel_pk_median_bf16(const unsigned short* __restrict__ X,
     if (MODE == MEDIAN) {
       // selection network, half at a time IN SOURCE ORDER: converting and
       // sorting [0,P/2) consumes only the first P/2 row loads, so those
-      // 240 CEs overlap the in-flight tail loads; then the (mirrored
+      // 191 CEs overlap the in-flight tail loads; then the (mirrored
       // descending) upper half, one split pass and two reductions.
       // MEDIAN pads split low/high so the fixed ranks P/2-1 / P/2 hit
       // the true median (low-pad key 0 only ties a negative-NaN data
@@ -560,16 +545,16 @@ colsel_pk_median_bf16(const unsigned short* __restrict__ X,
             }
         }
         if (h == 0) {
-          bitonic_sort_pk_half<P / 2, true>(
+          oem_sort_pk_half<P / 2, true>(
               *reinterpret_cast<u32(*)[P / 2]>(&v[0]));
           if (QUADS)
-            bitonic_sort_pk_half<P / 2, true>(
+            oem_sort_pk_half<P / 2, true>(
                 *reinterpret_cast<u32(*)[P / 2]>(&v2[0]));
         } else {
-          bitonic_sort_pk_half<P / 2, false>(
+          oem_sort_pk_half<P / 2, false>(
               *reinterpret_cast<u32(*)[P / 2]>(&v[P / 2]));
           if (QUADS)
-            bitonic_sort_pk_half<P / 2, false>(
+            oem_sort_pk_half<P / 2, false>(
                 *reinterpret_cast<u32(*)[P / 2]>(&v2[P / 2]));
         }
       }
@@ -676,6 +661,196 @@ colsel_pk_median_bf16(const unsigned short* __restrict__ X,
       o.s[0] = c0.s;
       o.s[1] = c1.s;
       if (!ROWS || unit < nunits) outw[pair + half] = o.w;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Median + Gram in ONE pass over X (bf16, 32 < n <= 64, even d).
+//
+// The median side is colsel_pk_median_bf16<64> unchanged: every lane holds
+// its column pair in 64 registers and runs the selection network, so the
+// result bits are the separate kernel's. What is new is that each lane also
+// drops its raw loaded words into an LDS image of the tile, and between
+// tiles the SAME four waves run the Gram MFMAs from that image. The two
+// phases are time-sliced inside a wave, so the only Gram state that lives
+// through a sort is 16 accumulator registers, and X is read once.
+//
+// Tile: 64 rows x 512 columns (256 lanes x one column pair). LDS image
+// [64][512] bf16 with a 16 B row pad (MG_ROW_BYTES = 1040, 66,560 B: two
+// blocks per CU):
+//  - store: lane t writes dword `row * 260 + t` — one base VGPR plus an
+//    immediate (63 * 1040 fits the 16-bit field); 32 consecutive lanes hit
+//    32 consecutive banks;
+//  - fragment read: in k-step s lane (r = l & 15, q = l >> 4) reads the
+//    16 B slot 16 * q + s of row r of a 16-row block. A Gram sums over k,
+//    so which 8 columns a (q, s) pair names is free as long as the A and B
+//    fragments agree, and over q < 4, s < 16 all 64 slots are covered.
+//    Bank row start = (4 * (65 * r + 16 * q + s)) mod 64 = 4 * ((r + s) mod
+//    16): distinct for the 16 rows whatever q they carry, so each of
+//    ds_read_b128's 16-lane groups — contiguous or not — is conflict-free.
+//
+// Wave w accumulates output rows [16w, 16w + 16) x all 64 columns as four
+// 16x16 tiles; tile j is column block (w + j) & 3, so fragment 0 is also
+// the A operand and a k-step costs 4 ds_read_b128 + 4 MFMAs with every
+// register index compile-time.
+//
+// The next tile's 64 raw words are loaded into a second register set right
+// after the current tile's words have been stored and turned into keys, so
+// they stay in flight through the whole sort and the MFMA phase: at two
+// waves per SIMD that prefetch, not occupancy, hides the HBM latency.
+//
+// Rows >= n and lanes past d / 2 put zeros in the image (their loads are
+// clamped to valid addresses and nothing is stored for them). Each block
+// owns a contiguous run of tiles and ends with one atomicAdd of its partial
+// Gram into the caller-zeroed G.
+// ---------------------------------------------------------------------------
+
+typedef __attribute__((ext_vector_type(8))) __bf16 mg_bf16x8;
+typedef __attribute__((ext_vector_type(4))) float mg_f32x4;
+
+constexpr int MG_THREADS = 256;
+constexpr int MG_PAIRS = MG_THREADS;               // column pairs per tile
+constexpr int MG_ROW_BYTES = MG_PAIRS * 4 + 16;    // 1040
+constexpr int MG_ROW_WORDS = MG_ROW_BYTES / 4;     // 260
+constexpr int MG_LDS_BYTES = 64 * MG_ROW_BYTES;    // 66,560
+
+// pinned load walk of one tile's 64 row words (see colsel_reg_kernel's load
+// phase); `p` is the lane's clamped pair in row 0
+template <int P>
+DEV void mg_load_tile(u32 (&r)[P], const u32* p, long rowstride, int n) {
+  if (n == P) {
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+      r[i] = *p;
+      if (i + 1 < P) p += rowstride;
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  } else {
+    const int n_walk = vecify(n);
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+      r[i] = *p;
+      p += (i + 1 < n_walk) ? rowstride : 0;
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+}
+
+__global__ void __launch_bounds__(MG_THREADS, 2)
+median_gram_bf16_kernel(const unsigned short* __restrict__ X,
+                        unsigned short* __restrict__ out,
+                        float* __restrict__ G, int n, long d,
+                        long tiles_per_block) {
+  constexpr int P = 64;
+  __shared__ __attribute__((aligned(16))) char img[MG_LDS_BYTES];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const long npairs = d >> 1;
+  const long rowstride = npairs;  // in u32 units
+  const long ntiles = (npairs + MG_PAIRS - 1) / MG_PAIRS;
+  const long t_lo = (long)blockIdx.x * tiles_per_block;
+  const long t_hi = min(ntiles, t_lo + tiles_per_block);
+  if (t_lo >= t_hi) return;  // the whole block leaves before any barrier
+
+  const u32* Xw = reinterpret_cast<const u32*>(X);
+  u32* outw = reinterpret_cast<u32*>(out);
+  u32* const wr = reinterpret_cast<u32*>(img) + tid;
+  const char* rd[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    rd[j] = img + (16 * ((wave + j) & 3) + (lane & 15)) * MG_ROW_BYTES +
+            (lane >> 4) * 256;
+
+  mg_f32x4 acc[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) acc[j] = mg_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+  const int nv = vecify(n);
+  // MEDIAN pad split, as in colsel_pk_median_bf16
+  const int n_lo = vecify(n + (P / 2 - 1 - ((n - 1) >> 1)));
+
+  u32 r[P];
+  mg_load_tile<P>(r, Xw + min(t_lo * MG_PAIRS + tid, npairs - 1), rowstride, n);
+
+  for (long t = t_lo; t < t_hi; ++t) {
+    const long pair = t * MG_PAIRS + tid;
+    const bool valid = pair < npairs;
+    u32 v[P];
+    // raw words into the image, then keys; r is dead after this
+    if (n == P && (t + 1) * MG_PAIRS <= npairs) {
+#pragma unroll
+      for (int i = 0; i < P; ++i) wr[i * MG_ROW_WORDS] = r[i];
+    } else {
+      const int n_img = valid ? nv : 0;
+#pragma unroll
+      for (int i = 0; i < P; ++i)
+        wr[i * MG_ROW_WORDS] = (i < n_img) ? r[i] : 0u;
+    }
+#pragma unroll
+    for (int i = 0; i < P; ++i) v[i] = pk_key_from_bf16(r[i]);
+    if (n < P) {
+#pragma unroll
+      for (int i = 0; i < P; ++i)
+        if (i >= nv) v[i] = (i < n_lo) ? 0u : 0xFFFFFFFFu;
+    }
+    if (t + 1 < t_hi)
+      mg_load_tile<P>(r, Xw + min(pair + MG_PAIRS, npairs - 1), rowstride, n);
+
+    oem_sort_pk_half<P / 2, true>(*reinterpret_cast<u32(*)[P / 2]>(&v[0]));
+    oem_sort_pk_half<P / 2, false>(
+        *reinterpret_cast<u32(*)[P / 2]>(&v[P / 2]));
+    u32 lo, hi;
+    pk_median_select<P>(v, lo, hi);
+    if (n & 1) hi = lo;
+    const float m0 =
+        0.5f * (key_to_float(lo & 0xFFFFu) + key_to_float(hi & 0xFFFFu));
+    const float m1 = 0.5f * (key_to_float(lo >> 16) + key_to_float(hi >> 16));
+    union { unsigned short s[2]; u32 w; } o;
+    union { unsigned short s; __hip_bfloat16 h; } c0, c1;
+    c0.h = __float2bfloat16(m0);
+    c1.h = __float2bfloat16(m1);
+    o.s[0] = c0.s;
+    o.s[1] = c1.s;
+    if (valid) outw[pair] = o.w;
+
+    __syncthreads();  // the image is complete
+    // k-step s + 1's four fragment reads issue ahead of k-step s's MFMAs
+    // (left alone the scheduler waits out every read in front of its MFMA);
+    // the group barriers pin that 4-read / 4-MFMA alternation
+    mg_bf16x8 f[2][4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      f[0][j] = *reinterpret_cast<const mg_bf16x8*>(rd[j]);
+    __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+      if (s + 1 < 16) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          f[(s + 1) & 1][j] =
+              *reinterpret_cast<const mg_bf16x8*>(rd[j] + (s + 1) * 16);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            f[s & 1][0], f[s & 1][j], acc[j], 0, 0, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);  // 4 LDS reads
+      __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);  // 4 MFMAs
+    }
+    __syncthreads();  // every wave has read it: the next tile may overwrite
+  }
+
+  // C/D map for 16x16: col = lane & 15, row = (lane >> 4) * 4 + reg
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int out_col = 16 * ((wave + j) & 3) + (lane & 15);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int out_row = 16 * wave + (lane >> 4) * 4 + q;
+      if (out_row < n && out_col < n)
+        atomicAdd(&G[(long)out_row * n + out_col], acc[j][q]);
     }
   }
 }
@@ -903,4 +1078,25 @@ void launch_colsel<__hip_bfloat16>(const __hip_bfloat16* X,
     return;
   }
   colsel_generic(X, out, n, d, mode, f, rows, n_src, stream);
+}
+
+// Persistent grid: two blocks per CU (what the 66,560 B image admits), each
+// with a contiguous run of tiles.
+void launch_median_gram_bf16(const __hip_bfloat16* X, __hip_bfloat16* med,
+                             float* G, int n, long d, hipStream_t stream) {
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
+                            dev) != hipSuccess ||
+      cus < 1)
+    cus = 256;
+  const long ntiles = ((d >> 1) + MG_PAIRS - 1) / MG_PAIRS;
+  const long want = 2L * cus;
+  const long blocks = ntiles < want ? ntiles : want;
+  const long tiles_per_block = (ntiles + blocks - 1) / blocks;
+  hipLaunchKernelGGL(median_gram_bf16_kernel, dim3((unsigned)blocks),
+                     dim3(MG_THREADS), 0, stream,
+                     reinterpret_cast<const unsigned short*>(X),
+                     reinterpret_cast<unsigned short*>(med), G, n, d,
+                     tiles_per_block);
 }

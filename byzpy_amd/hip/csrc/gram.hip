@@ -337,12 +337,14 @@ gram_bf16_lds_kernel(const __hip_bfloat16* __restrict__ X,
 
 // (A FUSED gram+median kernel lived here and was removed after SIX
 // measured variants all lost to the separate kernels — 32-60 ms vs
-// 6.9 ms at 64x125M. The median's per-chunk work only amortizes when
+// 6.9 ms at 64x125M. All six built the Gram's LDS image first and took
+// the median from it; the median's per-chunk work only amortizes when
 // each lane holds a full column (64 VGPRs of keys), which either
-// spills or halves occupancy inside the gram's register/LDS budget;
-// register-light organizations serialize on LDS merge chains or waste
-// 63/64 lanes on ballot descents. Full writeup:
-// profiles/r02_fusion_negative.md.)
+// spills or halves occupancy inside THIS kernel's register/LDS budget.
+// Full writeup: profiles/r02_fusion_negative.md. The fusion that ships
+// turns it round: median_gram_bf16_kernel in colsel.hip keeps the median
+// kernel's per-lane columns and lets the same waves run the Gram MFMAs
+// between tiles — profiles/r03_median_gram_fused.md.)
 
 // ---------------------------------------------------------------------------
 // LDS-staged f32 Gram (fast path for d % 4 == 0): same structure as the

@@ -32,6 +32,16 @@ template <typename T>
 void launch_colsel(const T* X, T* out, int n, long d, int mode, int f,
                    const int* rows, int n_src, hipStream_t stream);
 
+// colsel.hip: column median and Gram X X^T in one pass over X. bf16 only;
+// `med` receives what launch_colsel(mode 0) writes, bit for bit, and the
+// partial Grams are ADDED into the caller-zeroed (n, n) G. Call it only
+// where median_gram_bf16_applies(n, d).
+inline bool median_gram_bf16_applies(long n, long d) {
+  return n > 32 && n <= 64 && d >= 2 && (d % 2) == 0;
+}
+void launch_median_gram_bf16(const __hip_bfloat16* X, __hip_bfloat16* med,
+                             float* G, int n, long d, hipStream_t stream);
+
 // rsel.hip: streaming radix-select engine for large n, same modes.
 // `state` is caller-zeroed d*4 u32 scratch; `med` is a d-float scratch,
 // read only by mode 2 (may be null otherwise)

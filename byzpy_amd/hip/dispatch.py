@@ -9,6 +9,7 @@ plain GEMM shapes. CAF runs on the fused K9 matvec/colsum kernel pair.
 """
 from __future__ import annotations
 
+import os
 from typing import Optional, Sequence
 
 import torch
@@ -97,13 +98,48 @@ def gram(X: torch.Tensor) -> torch.Tensor:
     return Xf @ Xf.T
 
 
+# Column count from which median_and_gram takes the one-pass kernel
+# (colsel.hip: median_gram_bf16_kernel). Measured on MI355X at n = 64 and
+# n = 33, d = 64K ... 16M (profiles/r03_median_gram_fused.md, "d_min
+# sweep"): the fused call took 0.33-0.78 of the pair's time at EVERY size,
+# 64K included (11.2 vs 24.0 us at 64 x 65,536 — one launch against two).
+# 65,536 is the smallest size measured; below it the pair stays.
+MEDIAN_GRAM_FUSED_MIN_D = 65_536
+
+# BYZPY_MEDIAN_GRAM=split forces the two-kernel pair (A/B runs)
+_MEDIAN_GRAM_ENV = "BYZPY_MEDIAN_GRAM"
+
+
+def _median_gram_fused_ok(X: torch.Tensor) -> bool:
+    n, d = X.shape
+    return (
+        _gpu(X)
+        and X.dtype == torch.bfloat16
+        and 32 < n <= 64
+        and d % 2 == 0
+        and d >= MEDIAN_GRAM_FUSED_MIN_D
+        and os.environ.get(_MEDIAN_GRAM_ENV, "") != "split"
+    )
+
+
 def median_and_gram(X: torch.Tensor):
-    """Both flagship aggregates: (median, gram). Two separate kernels —
-    a fused single-HBM-pass kernel was built and measured across six
-    organizations and LOST to this pair every time (32-60 ms vs 6.9 at
-    64x125M; see profiles/r02_fusion_negative.md): the median work only
-    amortizes with full per-lane column residency, which cannot coexist
-    with the Gram's register/occupancy budget."""
+    """Both flagship aggregates: (median, gram). bf16 device matrices with
+    32 < n <= 64 rows and an even d >= MEDIAN_GRAM_FUSED_MIN_D take ONE
+    pass over X (``colsel(X, 0, 0, gram=G)``): every lane keeps its column
+    pair in registers and runs the median's selection network exactly as
+    the separate kernel does, drops the raw words into an LDS image on the
+    way, and the same waves run the Gram MFMAs from that image between
+    tiles (profiles/r03_median_gram_fused.md; the six organizations that
+    lost are in profiles/r02_fusion_negative.md). The median is bitwise
+    the separate kernel's; the Gram differs from ``gram(X)`` only in f32
+    summation order. Everything else, and ``BYZPY_MEDIAN_GRAM=split``,
+    runs ``median(X), gram(X)``."""
+    if _median_gram_fused_ok(X):
+        Xc = X.contiguous()
+        G = torch.empty((X.shape[0], X.shape[0]), dtype=torch.float32,
+                        device=X.device)
+        med = _hip.require().colsel(Xc, _COLSEL_MEDIAN, 0, gram=G)
+        return med, G
     return median(X), gram(X)
 
 

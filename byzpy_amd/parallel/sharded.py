@@ -45,8 +45,8 @@ def _global_gram(X_local: torch.Tensor) -> torch.Tensor:
 
 def median_and_multi_krum(X_local: torch.Tensor, f: int, q: int):
     """Both flagship aggregates with ONE collective: the local median
-    shard and the partial Gram (two kernels — the single-pass fusion was
-    measured slower and removed, see profiles/r02_fusion_negative.md),
+    shard and the partial Gram (D.median_and_gram: one pass over the shard
+    where the fused kernel applies, see profiles/r03_median_gram_fused.md),
     then one (n, n) all-reduce yields a Krum selection identical on
     every rank (RCCL all-reduce returns bitwise-identical sums on all
     ranks, so the winner set never diverges)."""
