@@ -6,6 +6,7 @@ from byzpy_amd.aggregators.coordinate_wise import (
 )
 from byzpy_amd.aggregators.geometric_wise import (
     Bulyan,
+    DnC,
     GeometricMedian,
     Krum,
     MinimumDiameterAveraging,
@@ -27,6 +28,7 @@ __all__ = [
     "MultiKrum",
     "Krum",
     "Bulyan",
+    "DnC",
     "GeometricMedian",
     "MinimumDiameterAveraging",
     "MoNNA",

@@ -69,6 +69,22 @@ def gram_feature_chunk(ref: Any, lo: int, hi: int) -> torch.Tensor:
         close_ref(c)
 
 
+def dnc_gram_chunk(
+    ref: Any, coords: torch.Tensor
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(partial centred Grams (niters, n, n), bad flags (niters, n)) of one
+    chunk ``coords`` (niters, bc) of DnC's sampled coordinates. Centring is
+    per column, so both are additive over the chunks."""
+    from byzpy_amd.hip import dispatch as D
+
+    X, c = resolve_matrix(ref)
+    try:
+        Gc, bad = D.dnc_gram(X, coords)
+        return Gc.clone(), bad.clone()
+    finally:
+        close_ref(c)
+
+
 def ref_dist_chunk(ref: Any, rlo: int, rhi: int, ref_index: int) -> torch.Tensor:
     """Squared distances of rows [rlo, rhi) to the reference row (MoNNA)."""
     X, c = resolve_matrix(ref)

@@ -138,6 +138,122 @@ class Bulyan(Aggregator):
             self._cleanup(handles)
 
 
+class DnC(Aggregator):
+    """Divide-and-Conquer (Shejwalkar & Houmansadr, NDSS 2021): ``niters``
+    times, sample b = min(subsample, d) coordinates, score every row by its
+    squared projection on the centred sample's top singular direction and
+    keep the n - floor(c f) lowest; average the rows kept every time. An
+    empty intersection returns zeros (skip the round).
+
+    Two departures from the paper: a row with a non-finite sampled entry
+    (inf, NaN, or |x| > 2^48) is never kept and does not enter the column
+    means; and coordinates are drawn WITH replacement (``torch.randint``,
+    sorted), so a draw is b integers, not a permutation of d.
+
+    ``coords`` fixes the sample: an int (niters, b) tensor, each row sorted
+    ascending, duplicates allowed. Otherwise every call draws from a CPU
+    generator (seeded by ``seed``, else torch's global one) and moves the
+    draw to the input's device, so one seed gives one sample on CPU and GPU.
+    For hipGraph capture pass ``coords`` as an int32 device tensor.
+
+    GPU: sampled centred Grams, spectral selection, counted gather-mean —
+    no host sync up to 128 rows. CPU pools: partial Grams over chunks of
+    ``chunk_size`` sampled coordinates."""
+
+    name = "dnc"
+    supports_subtasks = True
+    max_subtasks_inflight = 0
+
+    def __init__(
+        self,
+        f: int,
+        *,
+        niters: int = 5,
+        subsample: int = 10_000,
+        c: float = 1.0,
+        coords: "torch.Tensor | None" = None,
+        seed: "int | None" = None,
+        chunk_size: int = 2048,
+    ) -> None:
+        if f < 0:
+            raise ValueError("f must be >= 0")
+        if c < 0:
+            raise ValueError("c must be >= 0")
+        if niters < 1:
+            raise ValueError("niters must be >= 1")
+        if subsample < 1:
+            raise ValueError("subsample must be >= 1")
+        self.f, self.c = int(f), float(c)
+        self.niters, self.subsample = int(niters), int(subsample)
+        self.chunk_size = max(1, int(chunk_size))
+        self.coords = None
+        if coords is not None:
+            coords = torch.as_tensor(coords)
+            if coords.dim() != 2 or coords.shape[0] < 1 or coords.shape[1] < 1:
+                raise ValueError("coords must be (niters, b)")
+            if coords.dtype not in (torch.int32, torch.int64):
+                raise ValueError("coords must be int32 or int64")
+            if not coords.is_cuda and bool(
+                (coords[:, 1:] < coords[:, :-1]).any()
+            ):
+                raise ValueError("each row of coords must be sorted ascending")
+            self.coords = coords
+            self.niters = int(coords.shape[0])
+        self._gen = None
+        if seed is not None:
+            self._gen = torch.Generator(device="cpu")
+            self._gen.manual_seed(int(seed))
+
+    def _coords_for(self, X: torch.Tensor) -> torch.Tensor:
+        """The call's (niters, b) sample on X's device, after the checks that
+        need the shape of X."""
+        n, d = X.shape
+        F.dnc_keep(n, self.f, self.c)
+        if self.coords is not None:
+            co = self.coords
+            if not co.is_cuda and bool(((co < 0) | (co >= d)).any()):
+                raise ValueError(f"coords must lie in [0, {d})")
+            return co.to(X.device)
+        b = min(self.subsample, d)
+        draw = torch.randint(0, d, (self.niters, b), generator=self._gen)
+        return torch.sort(draw, dim=1).values.to(X.device)
+
+    def _aggregate(self, X: torch.Tensor) -> torch.Tensor:
+        return D.dnc(X, self.f, self._coords_for(X), self.c)
+
+    def create_subtasks(self, ctx: OpContext, **inputs: Any) -> Sequence[SubTask]:
+        gradients = inputs[self.input_key]
+        ref, X, like, handles = self._matrix_ref(ctx, gradients)
+        if X.is_cuda:
+            return []
+        try:
+            coords = self._coords_for(X)
+        except ValueError:
+            self._cleanup(handles)
+            raise
+        ctx.metadata["_op_pending"] = (X, like, handles)
+        b = coords.shape[1]
+        return [
+            SubTask(
+                fn=SF.dnc_gram_chunk,
+                args=(ref, coords[:, lo:hi].contiguous()),
+                name=f"dnc_gram[{lo}:{hi}]",
+            )
+            for lo, hi in chunk_ranges(b, min(self.chunk_size, b))
+        ]
+
+    def reduce_subtasks(self, ctx: OpContext, results: List[Any], **inputs: Any) -> Any:
+        X, like, handles = ctx.metadata.pop("_op_pending")
+        try:
+            Gc = sum(r[0] for r in results)
+            bad = sum(r[1] for r in results)
+            keep = F.dnc_keep(X.shape[0], self.f, self.c)
+            idx, count = D.dnc_select_from_gram(Gc, bad, keep)
+            return to_like(D.mean_rows_counted(X, idx, count), like)
+        finally:
+            self._cleanup(handles)
+
+
 class GeometricMedian(Aggregator):
     """Weiszfeld fixed point; barriered per-iteration fan-out on CPU pools
     (reference geometric_median.py:106-158), fused kernels on GPU."""

@@ -246,6 +246,30 @@ torch::Tensor mean_rows(torch::Tensor X, torch::Tensor idx) {
   return out;
 }
 
+// mean_rows(X, idx, count=c): the mean of rows idx[:c] with c an int32
+// device scalar read by the kernel (no host sync); zeros when c is 0.
+torch::Tensor mean_rows_counted(torch::Tensor X, torch::Tensor idx,
+                                torch::Tensor count) {
+  check_matrix(X);
+  check_i32(idx, 1, "idx");
+  TORCH_CHECK(idx.numel() >= 1 && idx.numel() <= INT_MAX,
+              "idx: expected at least one row");
+  TORCH_CHECK(count.is_cuda() && count.scalar_type() == torch::kInt32 &&
+                  count.numel() == 1,
+              "count: expected an int32 device scalar");
+  TORCH_CHECK(idx.device() == X.device() && count.device() == X.device(),
+              "idx, count: expected X's device");
+  const long d = (long)X.size(1);
+  const int k = (int)idx.numel();
+  auto out = torch::empty({d}, X.options());
+  by_dtype(X, [&](auto tag) {
+    using T = TAG_T(tag);
+    launch_mean_rows_counted<T>(ptr<T>(X), i32(idx), k, i32(count),
+                                ptr<T>(out), d, cur_stream());
+  });
+  return out;
+}
+
 torch::Tensor group_mean_rows(torch::Tensor X, torch::Tensor idx) {
   check_matrix(X);
   check_i32(idx, 2, "idx");
@@ -289,6 +313,37 @@ torch::Tensor gram(torch::Tensor X) {
     launch_gram<T>(ptr<T>(X), f32(G), n, d, cur_stream());
   });
   return G;
+}
+
+// gram(X, cols=c): the sampled centred Grams of DnC (gram.hip). cols is an
+// int32 (niters, b) device tensor of column indices (clamped to [0, d));
+// returns (Gc f32 (niters, n, n), bad int32 (niters, n)). Bitwise repeatable.
+std::vector<torch::Tensor> gram_sampled(torch::Tensor X, torch::Tensor cols) {
+  check_matrix(X);
+  check_i32(cols, 2, "cols");
+  TORCH_CHECK(cols.device() == X.device(), "cols: expected X's device");
+  const int64_t n = X.size(0);
+  const long d = (long)X.size(1);
+  const int64_t niters = cols.size(0), b = cols.size(1);
+  TORCH_CHECK(n >= 1 && n <= DNC_MAX_N, "gram(cols) supports 1 <= n <= ",
+              DNC_MAX_N, ", got ", n);
+  TORCH_CHECK(d >= 1, "gram(cols) needs at least one column");
+  TORCH_CHECK(niters >= 1 && niters <= 65535 && b >= 1 && b <= (1 << 30),
+              "cols: expected (niters, b) with 1 <= niters <= 65535 and ",
+              "1 <= b <= 2^30, got (", niters, ", ", b, ")");
+  int nchunks, tpc;
+  dnc_gram_chunks((int)b, (int)niters, nchunks, tpc);
+  auto part = torch::empty({niters * nchunks, n, n}, f32_like(X));
+  auto badpart = torch::empty({niters * nchunks, n}, i32_like(X));
+  auto Gc = torch::empty({niters, n, n}, f32_like(X));
+  auto bad = torch::empty({niters, n}, i32_like(X));
+  by_dtype(X, [&](auto tag) {
+    using T = TAG_T(tag);
+    launch_gram_sampled<T>(ptr<T>(X), i32(cols), (int)n, d, (int)niters,
+                           (int)b, f32(part), i32(badpart), f32(Gc), i32(bad),
+                           cur_stream());
+  });
+  return {Gc, bad};
 }
 
 // Fused Krum selection: Gram -> q winner indices (one kernel, replaces
@@ -471,6 +526,34 @@ torch::Tensor smea_select(torch::Tensor G, torch::Tensor combos) {
   return best;
 }
 
+// smea_select(Gc3, bad, keep): the DnC spectral selection (subsets.hip) on
+// the (niters, n, n) sampled centred Grams and their (niters, n) bad flags.
+// Returns (idx int32 (n,), count int32 ()): idx[:count] are the ascending
+// indices kept by every iteration, the rest is padding. No host sync.
+std::vector<torch::Tensor> dnc_select(torch::Tensor Gc3, torch::Tensor bad,
+                                      int64_t keep) {
+  TORCH_CHECK(Gc3.is_cuda() && Gc3.dim() == 3 && Gc3.size(1) == Gc3.size(2) &&
+                  Gc3.scalar_type() == torch::kFloat32 && Gc3.is_contiguous(),
+              "Gc3: expected an f32 contiguous device tensor (niters, n, n)");
+  const int64_t niters = Gc3.size(0), n = Gc3.size(1);
+  TORCH_CHECK(niters >= 1 && niters <= 65535, "Gc3: expected 1 <= niters <= ",
+              "65535, got ", niters);
+  TORCH_CHECK(n >= 1 && n <= DNC_MAX_N, "smea_select(Gc3, bad, keep) supports ",
+              "1 <= n <= ", DNC_MAX_N, ", got ", n);
+  check_i32(bad, 2, "bad");
+  TORCH_CHECK(bad.size(0) == niters && bad.size(1) == n &&
+                  bad.device() == Gc3.device(),
+              "bad: expected (", niters, ", ", n, ") on Gc3's device");
+  TORCH_CHECK(keep >= 1 && keep <= n, "keep: expected 1 <= keep <= ", n,
+              ", got ", keep);
+  auto kept = torch::empty({niters, n}, i32_like(Gc3));
+  auto idx = torch::empty({n}, i32_like(Gc3));
+  auto count = torch::empty({}, i32_like(Gc3));
+  launch_dnc_select(f32(Gc3), i32(bad), (int)niters, (int)n, (int)keep,
+                    i32(kept), i32(idx), i32(count), cur_stream());
+  return {idx, count};
+}
+
 // MDA two-pass device search: returns (found[npairs], subsets[npairs, m]);
 // the first found prefix (pair-lex order) holds the lex-smallest optimal
 // subset. No host sync anywhere.
@@ -588,9 +671,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("row_center_sqdists", &row_center_sqdists);
   m.def("row_scale", &row_scale);
   m.def("mean_rows", &mean_rows);
+  m.def("mean_rows", &mean_rows_counted,
+        "mean of rows idx[:count], count an int32 device scalar (K15)",
+        py::arg("X"), py::arg("idx"), py::kw_only(), py::arg("count"));
   m.def("group_mean_rows", &group_mean_rows);
   m.def("bucket_mean", &bucket_mean);
   m.def("gram", &gram);
+  m.def("gram", &gram_sampled,
+        "sampled centred Grams of DnC (K15): (Gc, bad)", py::arg("X"),
+        py::kw_only(), py::arg("cols"));
   m.def("krum_select", &krum_select, py::arg("G"), py::arg("f"), py::arg("q"),
         py::arg("iterative") = false);
   m.def("caf_matvec", &caf_matvec);
@@ -604,6 +693,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cc_apply", &cc_apply);
   m.def("mda_search", &mda_search, "exact min-diameter subset (host DFS)");
   m.def("smea_select", &smea_select, "device SMEA subset selection (K11)");
+  m.def("smea_select", &dnc_select,
+        "DnC spectral selection (K15): (idx, count)", py::arg("Gc3"),
+        py::arg("bad"), py::arg("keep"));
   m.def("little_fused", &little_fused, "fused Little attack (K14)");
   m.def("little_fused", &little_fused_stats,
         "Min-Max / Min-Sum statistics pass (K14): (mu, p, stats)",

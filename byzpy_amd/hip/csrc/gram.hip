@@ -1007,3 +1007,164 @@ void launch_gram<float>(const float* X, float* G, int n, long d,
   hipLaunchKernelGGL(gram_f32_kernel, grid, dim3(WAVES * 64), 0, stream, X, G,
                      n, d, kpb);
 }
+
+// ---------------------------------------------------------------------------
+// Sampled centred Gram (DnC, K15): per iteration t the
+// (n, n) Gram of the column sample X[:, cols[t]] after finite-aware
+// centring. n <= DNC_MAX_N.
+//
+// The work is latency-bound (n^2 b niters ~ 0.2 GFLOP; the cost is n b
+// niters scattered element reads), so the kernel is shaped for many
+// independent blocks, not for the matrix pipe: grid (column chunks, niters),
+// a block walks its chunk in tiles of DNC_TB columns. Per tile it gathers the
+// n x DNC_TB values by index into LDS (f32 or bf16 source), one lane per
+// column computes the mean over that column's finite entries and centres it
+// in place (a whole column is present, so no second pass over X), and the
+// 16 x 16 threads accumulate an RT x RT register block each of the n x n
+// partial with plain f32 FMAs. f32 MFMA has exactly the vector FMA rate on
+// gfx950, and the FMA loop adds every output entry in the same column order,
+// so two identical rows give bitwise identical Gram rows (exact score ties).
+//
+// No float atomics: a block stores its partial (and its rows' bad flags) in
+// a buffer of its own, and dnc_gram_reduce_kernel adds the partials in chunk
+// order, so the result is bitwise repeatable.
+// ---------------------------------------------------------------------------
+
+namespace {
+
+constexpr int DNC_TB = 64;        // columns per tile
+constexpr int DNC_THREADS = 256;  // 16 x 16 threads, RT x RT outputs each
+
+template <typename T, int RT>
+__global__ void __launch_bounds__(DNC_THREADS)
+dnc_gram_partial_kernel(const T* __restrict__ X, const int* __restrict__ cols,
+                        int n, long d, int b, int tiles_per_chunk,
+                        float* __restrict__ part, int* __restrict__ badpart) {
+  constexpr int NP = 16 * RT;
+  // [column][row], rows padded by one word: the gather writes one column per
+  // lane (stride NP + 1 words, conflict-free), the FMA loop reads rows
+  __shared__ float tile[DNC_TB][NP + 1];
+  __shared__ int cidx[DNC_TB];
+  __shared__ int badrow[NP];
+  const int tid = threadIdx.x;
+  const int ti = tid >> 4, tj = tid & 15;
+  const int t = blockIdx.y, chunk = blockIdx.x, nchunks = gridDim.x;
+  const int* tc = cols + (long)t * b;
+
+  float acc[RT][RT];
+#pragma unroll
+  for (int r = 0; r < RT; ++r)
+#pragma unroll
+    for (int s = 0; s < RT; ++s) acc[r][s] = 0.0f;
+  for (int i = tid; i < NP; i += DNC_THREADS) badrow[i] = 0;
+
+  const int c_begin = chunk * tiles_per_chunk * DNC_TB;
+  const int c_end = min(b, c_begin + tiles_per_chunk * DNC_TB);
+  for (int c0 = c_begin; c0 < c_end; c0 += DNC_TB) {
+    const int tb = min(DNC_TB, c_end - c0);
+    __syncthreads();  // the previous tile is consumed
+    if (tid < DNC_TB) {
+      long col = tid < tb ? (long)tc[c0 + tid] : 0;
+      col = col < 0 ? 0 : (col >= d ? d - 1 : col);
+      cidx[tid] = (int)col;
+    }
+    __syncthreads();
+    // gather: consecutive lanes take consecutive sampled columns of one row
+    for (int e = tid; e < NP * DNC_TB; e += DNC_THREADS) {
+      const int c = e & (DNC_TB - 1), i = e / DNC_TB;
+      float v = 0.0f;
+      if (i < n && c < tb) v = to_f<T>(X[(long)i * d + cidx[c]]);
+      tile[c][i] = v;
+    }
+    __syncthreads();
+    // finite-aware mean and centring, one lane per column, rows in order
+    if (tid < tb) {
+      float sum = 0.0f;
+      int cnt = 0;
+      for (int i = 0; i < n; ++i) {
+        const float v = tile[tid][i];
+        const bool ok = fabsf(v) <= DNC_MAX_ABS;  // false for NaN and inf
+        sum += ok ? v : 0.0f;
+        cnt += ok ? 1 : 0;
+      }
+      const float mu = cnt > 0 ? sum / (float)cnt : 0.0f;
+      for (int i = 0; i < n; ++i) {
+        const float v = tile[tid][i];
+        const bool ok = fabsf(v) <= DNC_MAX_ABS;
+        tile[tid][i] = ok ? v - mu : 0.0f;
+        if (!ok) badrow[i] = 1;  // every writer stores the same value
+      }
+    }
+    __syncthreads();
+    for (int c = 0; c < tb; ++c) {
+      float a[RT], bb[RT];
+#pragma unroll
+      for (int r = 0; r < RT; ++r) {
+        a[r] = tile[c][ti + 16 * r];
+        bb[r] = tile[c][tj + 16 * r];
+      }
+#pragma unroll
+      for (int r = 0; r < RT; ++r)
+#pragma unroll
+        for (int s = 0; s < RT; ++s) acc[r][s] = fmaf(a[r], bb[s], acc[r][s]);
+    }
+  }
+  __syncthreads();
+  const long slot = (long)t * nchunks + chunk;
+  float* P = part + slot * n * n;
+#pragma unroll
+  for (int r = 0; r < RT; ++r)
+#pragma unroll
+    for (int s = 0; s < RT; ++s) {
+      const int i = ti + 16 * r, j = tj + 16 * s;
+      if (i < n && j < n) P[(long)i * n + j] = acc[r][s];
+    }
+  for (int i = tid; i < n; i += DNC_THREADS) badpart[slot * n + i] = badrow[i];
+}
+
+// Gc[t] = sum of the nchunks partials of iteration t, in chunk order;
+// bad[t][i] = OR of the chunks' flags. grid (ceil(n*n / 256), niters).
+__global__ void __launch_bounds__(DNC_THREADS)
+dnc_gram_reduce_kernel(const float* __restrict__ part,
+                       const int* __restrict__ badpart, int n, int nchunks,
+                       float* __restrict__ Gc, int* __restrict__ bad) {
+  const int t = blockIdx.y;
+  const int nn = n * n;
+  const int e = blockIdx.x * DNC_THREADS + threadIdx.x;
+  const long base = (long)t * nchunks;
+  if (e < nn) {
+    float s = 0.0f;
+    for (int k = 0; k < nchunks; ++k) s += part[(base + k) * nn + e];
+    Gc[(long)t * nn + e] = s;
+  }
+  if (blockIdx.x == 0 && (int)threadIdx.x < n) {
+    int f = 0;
+    for (int k = 0; k < nchunks; ++k) f |= badpart[(base + k) * n + threadIdx.x];
+    bad[(long)t * n + threadIdx.x] = f != 0;
+  }
+}
+
+}  // namespace
+
+template <typename T>
+void launch_gram_sampled(const T* X, const int* cols, int n, long d,
+                         int niters, int b, float* part, int* badpart,
+                         float* Gc, int* bad, hipStream_t stream) {
+  int nchunks, tpc;
+  dnc_gram_chunks(b, niters, nchunks, tpc);
+  const dim3 grid(nchunks, niters);
+#define DNC_GRAM_LAUNCH(RT)                                                   \
+  hipLaunchKernelGGL((dnc_gram_partial_kernel<T, RT>), grid,                  \
+                     dim3(DNC_THREADS), 0, stream, X, cols, n, d, b, tpc,     \
+                     part, badpart)
+  if (n <= 16) DNC_GRAM_LAUNCH(1);
+  else if (n <= 32) DNC_GRAM_LAUNCH(2);
+  else if (n <= 64) DNC_GRAM_LAUNCH(4);
+  else DNC_GRAM_LAUNCH(8);
+#undef DNC_GRAM_LAUNCH
+  hipLaunchKernelGGL(dnc_gram_reduce_kernel,
+                     dim3((n * n + DNC_THREADS - 1) / DNC_THREADS, niters),
+                     dim3(DNC_THREADS), 0, stream, part, badpart, n, nchunks,
+                     Gc, bad);
+}
+INSTANTIATE_LAUNCHER(launch_gram_sampled)

@@ -53,6 +53,45 @@ void launch_rsel(int mode, const T* X, T* out, unsigned int* state, float* med,
 template <typename T>
 void launch_gram(const T* X, float* G, int n, long d, hipStream_t stream);
 
+// gram.hip / subsets.hip (K15, DnC). Row cap of both DnC kernels: the Gram
+// kernel's register blocks and the selection kernel's register-resident
+// matrix are sized by it.
+constexpr int DNC_MAX_N = 128;
+// A sampled entry counts as finite up to this magnitude (2^48): past it the
+// squares would overflow the f32 Gram, so the row is flagged bad like one
+// holding inf or NaN.
+constexpr float DNC_MAX_ABS = 281474976710656.0f;
+// Column chunking of launch_gram_sampled: tiles of 64 columns, grouped so
+// that nchunks * niters stays near one block per CU. The caller sizes the
+// partial buffers with it.
+inline void dnc_gram_chunks(int b, int niters, int& nchunks,
+                            int& tiles_per_chunk) {
+  const int ntiles = (b + 63) / 64;
+  int want = 256 / (niters < 1 ? 1 : niters);
+  if (want < 1) want = 1;
+  tiles_per_chunk = (ntiles + want - 1) / want;
+  nchunks = (ntiles + tiles_per_chunk - 1) / tiles_per_chunk;
+}
+// Per iteration t < niters: Gc[t] = C C^T (n, n) f32 of the sample
+// X[:, cols[t]] (cols: int32 (niters, b), clamped to [0, d)), C centred per
+// column by the mean of its finite entries, non-finite entries 0;
+// bad[t][i] = 1 where row i holds a non-finite sampled entry. part / badpart
+// are nchunks * niters * n * n floats / * n ints of scratch; the partials
+// are added in chunk order (bitwise repeatable). n <= DNC_MAX_N.
+template <typename T>
+void launch_gram_sampled(const T* X, const int* cols, int n, long d,
+                         int niters, int b, float* part, int* badpart,
+                         float* Gc, int* bad, hipStream_t stream);
+// Spectral selection on those Grams: per iteration a fixed-count power
+// iteration for the top eigenvector u, score_i = u_i^2 (+inf for bad rows),
+// kept_t = the `keep` lowest scores (ties to the smaller index) minus the
+// bad rows; idx receives the ascending indices of the intersection over t,
+// padded with 0 to n entries, count their number. kept is niters * n ints
+// of scratch. n <= DNC_MAX_N, 1 <= keep <= n.
+void launch_dnc_select(const float* Gc, const int* bad, int niters, int n,
+                       int keep, int* kept, int* idx, int* count,
+                       hipStream_t stream);
+
 // rowops.hip
 template <typename T>
 void launch_row_sqnorms(const T* X, float* out, int n, long d,
@@ -66,6 +105,12 @@ void launch_row_scale(const T* X, const float* s, T* out, int n, long d,
 template <typename T>
 void launch_mean_rows(const T* X, const int* idx, int k, T* out, long d,
                       hipStream_t stream);
+// The mean of rows idx[0 .. *count) with the count read on device (clamped
+// to [0, k]); zeros when it is 0. Entries of idx past the count are not read.
+template <typename T>
+void launch_mean_rows_counted(const T* X, const int* idx, int k,
+                              const int* count, T* out, long d,
+                              hipStream_t stream);
 template <typename T>
 void launch_group_mean_rows(const T* X, const int* idx, int g, int k, T* out,
                             long d, hipStream_t stream);

@@ -7,6 +7,8 @@
 //   mean_rows          gather-mean of selected rows -> (d,)
 //   group_mean_rows    per-group gather-mean -> (g,d)   (NNM mixing)
 //                                           gather_mean_kernel (both)
+//   mean_rows(count=)  the same over idx[:count], count read on the device
+//                                           gather_mean_counted_kernel
 //   bucket_mean        permuted segmented mean -> (nb,d) (Bucketing)
 //                                           bucket_mean_kernel
 //   weiszfeld_iter/_apply  w=1/max(dist,eps); z' = sum(w x)/sum(w); ||dz||^2
@@ -405,6 +407,27 @@ __global__ void gather_mean_kernel(const T* __restrict__ X,
       [&](long, float acc) { return acc * inv; });
 }
 
+// Counted variant (DnC): the row count is an int on the device, read here,
+// so a selection whose size is only known on the device needs no host sync.
+// A kernel of its own, not a flag on gather_mean_kernel: the un-counted
+// instantiations (mean_rows is in the flagship's timed region) keep their
+// arguments and instruction stream. Same col_wsum association over
+// idx[0 .. count), so the result is bitwise that of mean_rows on idx[:count];
+// count 0 writes zeros.
+template <typename T, bool VEC>
+__global__ void gather_mean_counted_kernel(const T* __restrict__ X,
+                                           const int* __restrict__ idx, int k,
+                                           const int* __restrict__ count,
+                                           T* __restrict__ out, long d) {
+  const int cnt = min(max(*count, 0), k);
+  const float inv = cnt > 0 ? 1.0f / (float)cnt : 0.0f;
+  const long start = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long stride = (long)gridDim.x * blockDim.x;
+  col_wsum<T, VEC>(
+      X, out, d, start, stride, 0, cnt, [&](int i) { return idx[i]; },
+      [](int) { return 1.0f; }, [&](long, float acc) { return acc * inv; });
+}
+
 template <typename T, bool VEC>
 __global__ void bucket_mean_kernel(const T* __restrict__ X,
                                    const int* __restrict__ perm, int n,
@@ -669,6 +692,18 @@ void launch_mean_rows(const T* X, const int* idx, int k, T* out, long d,
 }
 
 template <typename T>
+void launch_mean_rows_counted(const T* X, const int* idx, int k,
+                              const int* count, T* out, long d,
+                              hipStream_t stream) {
+  by_vec<T>(d, [&](auto v) {
+    const long work = col_work<T, VEC_OF(v)>(d);
+    hipLaunchKernelGGL((gather_mean_counted_kernel<T, VEC_OF(v)>),
+                       dim3(col_grid(work, BLOCK)), dim3(BLOCK), 0, stream, X,
+                       idx, k, count, out, d);
+  });
+}
+
+template <typename T>
 void launch_group_mean_rows(const T* X, const int* idx, int g, int k, T* out,
                             long d, hipStream_t stream) {
   by_vec<T>(d, [&](auto v) {
@@ -743,6 +778,7 @@ INSTANTIATE_LAUNCHER(launch_row_center_sqdists)
 INSTANTIATE_LAUNCHER(launch_grouped_weiszfeld)
 INSTANTIATE_LAUNCHER(launch_row_scale)
 INSTANTIATE_LAUNCHER(launch_mean_rows)
+INSTANTIATE_LAUNCHER(launch_mean_rows_counted)
 INSTANTIATE_LAUNCHER(launch_group_mean_rows)
 INSTANTIATE_LAUNCHER(launch_bucket_mean)
 INSTANTIATE_LAUNCHER(launch_weiszfeld_update)

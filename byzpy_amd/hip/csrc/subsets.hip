@@ -274,7 +274,155 @@ mda_dfs_kernel(const float* __restrict__ D2g, const int* __restrict__ prefixes,
   }
 }
 
+// ---------------------------------------------------------------------------
+// DnC spectral selection (K15)
+// ---------------------------------------------------------------------------
+
+// One block per iteration t. The SMEA Jacobi above is one wave rotating one
+// pair at a time: n (n - 1) / 2 * SMEA_SWEEPS serial rotations is ~80,000
+// barrier pairs at n = 128. DnC needs only the TOP eigenvector, so this is a
+// fixed-count power iteration instead: no data-dependent trip count, two
+// barriers per step.
+//
+// Thread (r, i) keeps A[16 r .. 16 r + 15][i] of the scaled matrix
+// A = Gc / max diag in registers (A is symmetric, so that column segment is
+// the row segment of y_i = sum_k A[i][k] v[k]; consecutive lanes read
+// consecutive words of Gc). A step is 16 FMAs per thread against v in LDS,
+// then one thread per row adds its <= 8 segment partials in segment order:
+// every row is summed in the same order, so identical Gram rows give
+// bitwise identical scores and ties resolve by index alone.
+//
+// |A_ij| <= 1 and 1 <= lambda_max(A) <= n, so v grows by at most 2^7 per
+// step and never loses its top component: it is renormalised every
+// DNC_NORM_EVERY steps only. The start vector is e_i0, i0 the first row at
+// the largest diagonal entry (the all-ones vector is A's null vector).
+// score_i = u_i^2 ranks like lambda u_i^2. With the two top eigenvalues at
+// ratio rho the error left is rho^DNC_POWER_STEPS: 1e-6 at rho = 0.9.
+
+constexpr int DNC_SEL_THREADS = 1024;
+constexpr int DNC_SEG = 16;  // matrix rows per thread
+constexpr int DNC_MAX_SEGS = DNC_MAX_N / DNC_SEG;
+constexpr int DNC_POWER_STEPS = 128;
+constexpr int DNC_NORM_EVERY = 8;
+static_assert(DNC_MAX_SEGS * DNC_MAX_N <= DNC_SEL_THREADS, "one thread per (segment, row)");
+static_assert(DNC_POWER_STEPS % DNC_NORM_EVERY == 0, "ends normalised");
+
+__global__ void __launch_bounds__(DNC_SEL_THREADS)
+dnc_scores_kernel(const float* __restrict__ Gc3, const int* __restrict__ bad,
+                  int n, int keep, int* __restrict__ kept) {
+  __shared__ float v[DNC_MAX_N];
+  __shared__ float part[DNC_MAX_SEGS][DNC_MAX_N];
+  __shared__ float score[DNC_MAX_N];
+  const int tid = threadIdx.x;
+  const int t = blockIdx.x;
+  const float* G = Gc3 + (long)t * n * n;
+  const int segs = (n + DNC_SEG - 1) / DNC_SEG;
+  const int i = tid % n, r = tid / n;
+  const bool active = r < segs;
+
+  // scale and start row from the diagonal (staged in `score`)
+  if (tid < DNC_MAX_N) {
+    const float g = tid < n ? G[(long)tid * n + tid] : 0.0f;
+    score[tid] = (g > 0.0f && g < INFINITY) ? g : 0.0f;
+    v[tid] = 0.0f;
+  }
+  __syncthreads();
+  float dmax = 0.0f;
+  int i0 = 0;
+  for (int k = 0; k < n; ++k)
+    if (score[k] > dmax) { dmax = score[k]; i0 = k; }
+  const float scale = dmax > 0.0f ? 1.0f / dmax : 0.0f;
+  float a[DNC_SEG];
+#pragma unroll
+  for (int m = 0; m < DNC_SEG; ++m) {
+    const int k = r * DNC_SEG + m;
+    float x = (active && k < n) ? G[(long)k * n + i] * scale : 0.0f;
+    if (!(fabsf(x) <= 2.0f)) x = 0.0f;  // a non-finite Gram entry
+    a[m] = x;
+  }
+  __syncthreads();
+  if (tid == i0) v[tid] = 1.0f;
+  __syncthreads();
+
+  for (int step = 0; step < DNC_POWER_STEPS; ++step) {
+    if (active) {
+      float p = 0.0f;
+#pragma unroll
+      for (int m = 0; m < DNC_SEG; ++m) p = fmaf(a[m], v[r * DNC_SEG + m], p);
+      part[r][i] = p;
+    }
+    __syncthreads();
+    if (tid < n) {
+      float y = 0.0f;
+      for (int s = 0; s < segs; ++s) y += part[s][tid];
+      v[tid] = y;
+    }
+    __syncthreads();
+    if ((step + 1) % DNC_NORM_EVERY == 0) {
+      float nrm2 = 0.0f;
+      for (int k = 0; k < n; ++k) nrm2 += v[k] * v[k];
+      const float inv = nrm2 > 0.0f ? rsqrtf(nrm2) : 0.0f;
+      __syncthreads();
+      if (tid < n) v[tid] *= inv;
+      __syncthreads();
+    }
+  }
+
+  if (tid < n)
+    score[tid] = bad[(long)t * n + tid] != 0 ? INFINITY : v[tid] * v[tid];
+  __syncthreads();
+  if (tid < n) {
+    const float s = score[tid];
+    int rank = 0;
+    for (int j = 0; j < n; ++j) {
+      const float sj = score[j];
+      rank += (sj < s || (sj == s && j < tid)) ? 1 : 0;
+    }
+    kept[(long)t * n + tid] = (rank < keep && s < INFINITY) ? 1 : 0;
+  }
+}
+
+// good = AND over iterations of kept_t, compacted ascending; one block.
+__global__ void __launch_bounds__(DNC_MAX_N)
+dnc_intersect_kernel(const int* __restrict__ kept, int niters, int n,
+                     int* __restrict__ idx, int* __restrict__ count) {
+  __shared__ int good[DNC_MAX_N];
+  const int tid = threadIdx.x;
+  if (tid < n) {
+    int g = 1;
+    for (int t = 0; t < niters; ++t) g &= kept[(long)t * n + tid];
+    good[tid] = g;
+  }
+  __syncthreads();
+  if (tid < n) {
+    int before = 0, total = 0;
+    for (int j = 0; j < n; ++j) {
+      before += j < tid ? good[j] : 0;
+      total += good[j];
+    }
+    if (good[tid]) idx[before] = tid;
+    // the bad rows fill the tail in order, so every slot is written once
+    else idx[total + (tid - before)] = 0;
+    if (tid == 0) *count = total;
+  }
+}
+
 }  // namespace
+
+void launch_dnc_select(const float* Gc, const int* bad, int niters, int n,
+                       int keep, int* kept, int* idx, int* count,
+                       hipStream_t stream) {
+  // one thread per (segment, row), whole waves, and at least the DNC_MAX_N
+  // threads that clear the LDS vectors; no idle waves at the barriers
+  // (measured: no faster than a fixed 1024 at n = 64, 65 us either way)
+  const int segs = (n + DNC_SEG - 1) / DNC_SEG;
+  int threads = ((segs * n + 63) / 64) * 64;
+  if (threads < DNC_MAX_N) threads = DNC_MAX_N;
+  hipLaunchKernelGGL(dnc_scores_kernel, dim3(niters), dim3(threads), 0, stream,
+                     Gc, bad, n, keep, kept);
+  hipLaunchKernelGGL(dnc_intersect_kernel, dim3(1), dim3(DNC_MAX_N), 0, stream,
+                     kept, niters, n, idx, count);
+}
 
 void launch_smea_select(const float* G, const int* combos, int n, int m,
                         int C, unsigned long long* best, hipStream_t stream) {

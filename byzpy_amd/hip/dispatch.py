@@ -2,8 +2,8 @@
 
 CPU tensors -> byzpy_amd.ops.functional (pure torch, the parity oracle).
 CUDA(ROCm) tensors -> hand-written gfx950 kernels in byzpy_amd/_hip_ops
-(SURVEY.md §2.7 kernel inventory K1-K14). Ops whose GPU path composes
-library GEMMs / batched eig (SMEA combos, attacks) run the functional
+(SURVEY.md §2.7 kernel inventory K1-K14, plus K15 for DnC). Ops whose GPU
+path composes library GEMMs / batched eig (SMEA combos, attacks) run the functional
 torch path on-device — rocBLAS library GEMMs are the sanctioned path for
 plain GEMM shapes. CAF runs on the fused K9 matvec/colsum kernel pair.
 """
@@ -285,6 +285,141 @@ def mean_rows(X: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     if _gpu(X):
         return _hip.require().mean_rows(X.contiguous(), idx.to(torch.int32))
     return X.float()[idx].mean(dim=0).to(X.dtype)
+
+
+def mean_rows_counted(
+    X: torch.Tensor, idx: torch.Tensor, count: torch.Tensor
+) -> torch.Tensor:
+    """Mean of rows idx[:count] with ``count`` an int32 scalar tensor that a
+    device X reads on the device (no host sync); zeros when it is 0. Bitwise
+    ``mean_rows(X, idx[:count])`` otherwise."""
+    if _gpu(X):
+        return _hip.require().mean_rows(
+            X.contiguous(), idx.to(torch.int32), count=count.to(torch.int32)
+        )
+    k = int(count)
+    if k == 0:
+        return torch.zeros_like(X[0])
+    return X.float()[idx[:k].long()].mean(dim=0).to(X.dtype)
+
+
+# -- DnC (K15) ---------------------------------------------------------------
+#
+# Divide-and-Conquer (Shejwalkar & Houmansadr 2021): per iteration a sample of
+# b coordinates, the centred sample's top singular direction, the rows with
+# the largest squared projection on it dropped; the rows kept by every
+# iteration are averaged. Everything after the (niters, n, n) sampled centred
+# Grams is O(n^2): lambda u_i^2 from the Gram's top eigenpair IS the squared
+# projection, so no d-sized vector is formed. ops/functional.py keeps its own
+# text as the oracle.
+
+# Row cap of gram(X, cols=) and smea_select(Gc3, bad, keep) (DNC_MAX_N in
+# csrc/launchers.h).
+DNC_MAX_N = 128
+
+
+def _dnc_fused(T: torch.Tensor, n: int) -> bool:
+    return _gpu(T) and 1 <= n <= DNC_MAX_N
+
+
+def dnc_gram(X: torch.Tensor, coords: torch.Tensor):
+    """(Gc (niters, n, n), bad int32 (niters, n)) of the samples
+    X[:, coords[t]]: Gc[t] = C C^T with C centred per column by the mean of
+    its finite entries (|x| <= 2^48) and 0 where an entry is not; bad marks
+    the rows holding such an entry. Additive over column chunks of coords.
+    One fused launch pair to DNC_MAX_N rows on device (f32, bitwise
+    repeatable); else f64 torch ops."""
+    if _dnc_fused(X, X.shape[0]):
+        cols = coords.to(device=X.device, dtype=torch.int32).contiguous()
+        Gc, bad = _hip.require().gram(X.contiguous(), cols=cols)
+        return Gc, bad
+    return _dnc_gram_torch(X, coords)
+
+
+def _dnc_gram_torch(X: torch.Tensor, coords: torch.Tensor):
+    """dnc_gram as f64 torch ops, any device."""
+    S = X[:, coords.to(X.device).long()].permute(1, 0, 2).double()  # (t, n, b)
+    ok = torch.isfinite(S) & (S.abs() <= F.DNC_MAX_ABS)
+    Sz = torch.where(ok, S, torch.zeros_like(S))
+    mu = Sz.sum(dim=1, keepdim=True) / ok.sum(dim=1, keepdim=True).clamp_min(1)
+    C = torch.where(ok, S - mu, torch.zeros_like(S))
+    bad = (~ok.all(dim=2)).to(torch.int32)
+    return torch.bmm(C, C.transpose(1, 2)), bad
+
+
+def dnc_select_from_gram(Gc: torch.Tensor, bad: torch.Tensor, keep: int):
+    """(idx int32 (n,), count int32 ()) from the sampled centred Grams:
+    idx[:count] are the ascending indices of the rows that every iteration
+    keeps (its ``keep`` lowest lambda u_i^2, ties to the smaller index, bad
+    rows never), the rest of idx is padding. One fused launch pair on device
+    for f32 Grams to DNC_MAX_N rows, no host sync; else torch ops with an
+    f64 ``eigh`` (which syncs)."""
+    niters, n = bad.shape
+    if not 1 <= keep <= n:
+        raise ValueError(f"DnC needs 1 <= keep <= n, got keep={keep}, n={n}")
+    if _dnc_fused(Gc, n) and Gc.dtype == torch.float32:
+        idx, count = _hip.require().smea_select(
+            Gc.contiguous(), bad.to(torch.int32).contiguous(), int(keep)
+        )
+        return idx, count
+    return _dnc_select_torch(Gc, bad, keep)
+
+
+def _dnc_select_torch(Gc: torch.Tensor, bad: torch.Tensor, keep: int):
+    """dnc_select_from_gram as torch ops, any device; eigh syncs the host."""
+    G = Gc.double()
+    lam, U = torch.linalg.eigh(G)
+    top, u = lam[:, -1], U[:, :, -1]
+    # G u summed row by row: identical Gram rows get identical scores
+    y = (G * u[:, None, :]).sum(dim=2)
+    score = torch.where(
+        top[:, None] > 0, y * y / top[:, None].clamp_min(1e-300),
+        torch.zeros_like(y),
+    )
+    isbad = bad != 0
+    score = score.masked_fill(isbad, float("inf"))
+    order = torch.argsort(score, dim=1, stable=True)
+    kept = torch.zeros_like(isbad)
+    kept.scatter_(1, order[:, :keep], True)
+    good = (kept & ~isbad).all(dim=0)
+    idx = torch.argsort((~good).to(torch.int8), stable=True).to(torch.int32)
+    idx = torch.where(good[idx.long()], idx, torch.zeros_like(idx))
+    return idx, good.sum().to(torch.int32)
+
+
+def _dnc_idx(X: torch.Tensor, f: int, coords: torch.Tensor, c: float):
+    keep = F.dnc_keep(X.shape[0], f, c)
+    Gc, bad = dnc_gram(X, coords)
+    return dnc_select_from_gram(Gc, bad, keep)
+
+
+def dnc_select(
+    X: torch.Tensor, f: int, coords: torch.Tensor, c: float = 1.0
+) -> torch.Tensor:
+    """DnC's good set as a bool (n,) mask (see ``dnc``)."""
+    if not _gpu(X):
+        return F.dnc_select(X, f, coords, c)
+    n = X.shape[0]
+    idx, count = _dnc_idx(X, f, coords, c)
+    live = (torch.arange(n, device=X.device) < count).to(torch.int32)
+    hits = torch.zeros(n, dtype=torch.int32, device=X.device)
+    return hits.scatter_add_(0, idx.long(), live) > 0
+
+
+def dnc(
+    X: torch.Tensor, f: int, coords: torch.Tensor, c: float = 1.0
+) -> torch.Tensor:
+    """DnC: the mean of the rows that survive every iteration's spectral
+    filter on the sample X[:, coords[t]]; zeros if none does (skip the
+    round). ``coords`` is int (niters, b), each row sorted, duplicates
+    allowed. On device to DNC_MAX_N rows: sampled centred Grams, spectral
+    selection, counted gather-mean — three binding calls, no host sync,
+    capturable into a hipGraph when coords is an int32 device tensor. Past
+    it the same steps as torch ops on the device."""
+    if not _gpu(X):
+        return F.dnc(X, f, coords, c)
+    idx, count = _dnc_idx(X, f, coords, c)
+    return mean_rows_counted(X, idx, count)
 
 
 def group_mean_rows(X: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:

@@ -171,6 +171,81 @@ def bulyan(X: torch.Tensor, f: int) -> torch.Tensor:
     return mean_of_medians(X[sel], 2 * f)
 
 
+# DnC (Shejwalkar & Houmansadr, NDSS 2021, Algorithm 2). A sampled entry is
+# "finite" up to this magnitude; past it (and for inf / NaN) its row is bad:
+# the square of a larger value does not fit the f32 Gram of the device path.
+DNC_MAX_ABS = float(2**48)
+
+
+def dnc_keep(n: int, f: int, c: float = 1.0) -> int:
+    """Rows each DnC iteration keeps: n - floor(c f)."""
+    if f < 0 or c < 0:
+        raise ValueError(f"DnC needs f >= 0 and c >= 0, got f={f}, c={c}")
+    keep = n - int(math.floor(c * f))
+    if keep < 1:
+        raise ValueError(
+            f"DnC needs n - floor(c f) >= 1, got n={n}, f={f}, c={c}"
+        )
+    return keep
+
+
+def _dnc_kept(S: torch.Tensor, keep: int) -> torch.Tensor:
+    """One DnC iteration on the (n, b) sample S: bool (n,) of kept rows."""
+    n = S.shape[0]
+    Sd = S.detach().float().double().cpu()
+    ok = torch.isfinite(Sd) & (Sd.abs() <= DNC_MAX_ABS)
+    Sz = torch.where(ok, Sd, torch.zeros_like(Sd))
+    cnt = ok.sum(dim=0)
+    mu = Sz.sum(dim=0) / cnt.clamp_min(1)
+    C = torch.where(ok, Sd - mu[None, :], torch.zeros_like(Sd))
+    bad = ~ok.all(dim=1)
+    lam, U = torch.linalg.eigh(C @ C.T)
+    top, u = float(lam[-1]), U[:, -1]
+    # lambda u_i^2 is the squared projection of row i on the top right
+    # singular vector r = C^T u / sqrt(lambda). Projecting row by row, each
+    # row summed alone, gives identical rows identical scores (eigh's u_i
+    # agree only to rounding), so the index tie-break below is exact.
+    if top > 0.0:
+        r = (C * u[:, None]).sum(dim=0)
+        score = (C * r[None, :]).sum(dim=1) ** 2 / top
+    else:
+        score = torch.zeros(n, dtype=torch.float64)
+    score = torch.where(bad, torch.full_like(score, float("inf")), score)
+    order = sorted(range(n), key=lambda i: (float(score[i]), i))
+    kept = torch.zeros(n, dtype=torch.bool)
+    kept[order[:keep]] = True
+    return kept & ~bad
+
+
+def dnc_select(
+    X: torch.Tensor, f: int, coords: torch.Tensor, c: float = 1.0
+) -> torch.Tensor:
+    """DnC's good set, bool (n,): per row t of ``coords`` (int (niters, b)
+    column indices, duplicates allowed) the n - floor(c f) rows with the
+    lowest outlier score on the sample X[:, coords[t]] — the squared
+    projection of the centred row on the sample's top right singular
+    vector — and the intersection over t. Columns are centred by the mean of
+    their finite entries, a non-finite entry counts 0, and a row with one in
+    the sample is never kept. f64 throughout; this is the oracle."""
+    keep = dnc_keep(X.shape[0], f, c)
+    good = torch.ones(X.shape[0], dtype=torch.bool)
+    for row in coords.detach().cpu().long():
+        good &= _dnc_kept(X[:, row.to(X.device)], keep)
+    return good
+
+
+def dnc(
+    X: torch.Tensor, f: int, coords: torch.Tensor, c: float = 1.0
+) -> torch.Tensor:
+    """DnC: the mean (f32) of the rows of dnc_select; the zero vector when
+    no row survives every iteration (skip the round). Rows outside the good
+    set are not read, so an inf in one never reaches the result."""
+    good = dnc_select(X, f, coords, c).to(X.device)
+    if not bool(good.any()):
+        return torch.zeros_like(X[0])
+    return X[good].float().mean(dim=0).to(X.dtype)
+
+
 def geometric_median(
     X: torch.Tensor,
     *,

@@ -69,6 +69,22 @@ def bulyan(X_local: torch.Tensor, f: int) -> torch.Tensor:
     return D.mean_of_medians(X_local, 2 * f, rows=sel)
 
 
+def dnc(
+    X_local: torch.Tensor, f: int, coords_local: torch.Tensor, c: float = 1.0
+) -> torch.Tensor:
+    """DnC on a d-shard. ``coords_local`` (niters, b_local) indexes the
+    LOCAL shard: every rank samples its own coordinates (the global sample
+    is their union; ranks agree on niters). Columns are centred one by one,
+    so the centred Gram is additive over ranks: one all-reduce of the
+    (niters, n, n) partials and one of the bad flags, then the selection —
+    identical on every rank, as the all-reduce returns the same bits to
+    all — and the counted mean of the local shard."""
+    keep = F.dnc_keep(X_local.shape[0], f, c)
+    Gc, bad = D.dnc_gram(X_local, coords_local)
+    idx, count = D.dnc_select_from_gram(all_reduce_(Gc), all_reduce_(bad), keep)
+    return D.mean_rows_counted(X_local, idx, count)
+
+
 def krum(X_local: torch.Tensor, f: int) -> torch.Tensor:
     scores = D.krum_scores_from_gram(_global_gram(X_local), f)
     return X_local[int(torch.argmin(scores))].clone()
