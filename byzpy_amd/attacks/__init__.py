@@ -1,5 +1,6 @@
 from byzpy_amd.attacks.base import Attack
 from byzpy_amd.attacks.ops import (
+    AGRTailoredAttack,
     EmpireAttack,
     GaussianAttack,
     InfAttack,
@@ -22,4 +23,5 @@ __all__ = [
     "MimicAttack",
     "MinMaxAttack",
     "MinSumAttack",
+    "AGRTailoredAttack",
 ]

@@ -105,6 +105,44 @@ class MinSumAttack(_CloudBoundAttack):
     _op = staticmethod(D.min_sum)
 
 
+class AGRTailoredAttack(Attack):
+    """Aggregator-tailored attack (Shejwalkar & Houmansadr 2021): the f
+    Byzantine workers all send mu + gamma * p with the largest gamma for
+    which ``agr`` ("krum", "multi-krum" with ``q`` winners, default all
+    honest rows' count, or "bulyan"), run with parameter f on the honest
+    gradients plus those f copies, still selects them."""
+
+    name = "attack/agr-tailored"
+    uses_honest_grads = True
+
+    def __init__(
+        self,
+        f: int,
+        agr: str = "multi-krum",
+        *,
+        q: Optional[int] = None,
+        perturbation: str = "std",
+        chunk_size: int = 8192,
+    ) -> None:
+        if f < 1:
+            raise ValueError("f must be >= 1")
+        if agr not in F.AGR_RULES:
+            raise ValueError(f"agr must be one of {F.AGR_RULES}, got {agr!r}")
+        if q is not None and q < 1:
+            raise ValueError("q must be >= 1")
+        D._perturb_code(perturbation)  # ValueError on an unknown name
+        self.f = int(f)
+        self.agr = agr
+        self.q = None if q is None else int(q)
+        self.perturbation = perturbation
+        self.chunk_size = int(chunk_size)
+
+    def apply(self, *, honest_grads: Any) -> Any:
+        X, like = self._stack(honest_grads)
+        out = D.agr_tailored(X, self.f, self.agr, self.q, self.perturbation)
+        return to_like(out, like)
+
+
 class GaussianAttack(Attack):
     """iid N(mu, sigma^2) noise vector; seedable for determinism."""
 

@@ -374,6 +374,53 @@ torch::Tensor krum_select(torch::Tensor G, int64_t f, int64_t q,
   return idx;
 }
 
+// krum_select(G, f, q, stats=, rule=[, gammas=]): the aggregator-tailored
+// attack search (krumsel.hip). G is the f32 Gram of the n honest rows, stats
+// the 2n + 1 statistics of little_fused(X, z, perturb), f >= 1 the number of
+// copies of m(gamma) = mu + gamma p appended; rule 0 is Krum / Multi-Krum
+// with q winners, rule 1 Bulyan (q ignored). With gammas (f32 device vector
+// of B trial values): int32 (B,) flags, 1 where the rule still selects the
+// malicious rows. Without: the f32 0-dim gamma found by the device grid
+// search. No host sync either way.
+torch::Tensor agr_search(torch::Tensor G, int64_t f, int64_t q,
+                         torch::Tensor stats, int64_t rule,
+                         c10::optional<torch::Tensor> gammas) {
+  check_gram(G, "G");
+  const int64_t n = G.size(0);
+  TORCH_CHECK(rule == AGR_RULE_KRUM || rule == AGR_RULE_BULYAN,
+              "rule: expected 0 (Krum / Multi-Krum) or 1 (Bulyan), got ", rule);
+  TORCH_CHECK(f >= 1 && n >= 2 && f <= n,
+              "krum_select(stats) needs f >= 1, n >= 2, f <= n, got n=", n,
+              ", f=", f);
+  TORCH_CHECK(n + f <= KRUM_ITER_MAX_N, "krum_select(stats) supports n + f <= ",
+              KRUM_ITER_MAX_N, ", got ", n + f);
+  if (rule == AGR_RULE_BULYAN) {
+    TORCH_CHECK(n >= 3 * f + 3, "Bulyan needs n + f >= 4f + 3, got n=", n,
+                ", f=", f);
+  } else {
+    TORCH_CHECK(q >= 1 && q <= n + f, "q: expected 1 <= q <= n + f, got ", q);
+  }
+  check_f32_vector(stats, 2 * n + 1, "stats");
+  TORCH_CHECK(stats.device() == G.device(), "stats: expected G's device");
+  if (gammas.has_value()) {
+    const int64_t B = gammas->numel();
+    TORCH_CHECK(B >= 1 && B <= 65535, "gammas: expected 1 to 65535 values");
+    check_f32_vector(*gammas, B, "gammas");
+    TORCH_CHECK(gammas->device() == G.device(), "gammas: expected G's device");
+    auto flags = torch::empty({B}, i32_like(G));
+    launch_agr_flags(f32(G), f32(stats), (int)n, (int)f, (int)q, (int)rule,
+                     f32(*gammas), (int)B, i32(flags), cur_stream());
+    return flags;
+  }
+  auto state = torch::empty({AGR_STATE_FLOATS}, f32_like(G));
+  auto flags =
+      torch::empty({AGR_GEO_POINTS + 2 * AGR_LIN_POINTS}, i32_like(G));
+  auto gamma = torch::empty({}, f32_like(G));
+  launch_agr_search(f32(G), f32(stats), (int)n, (int)f, (int)q, (int)rule,
+                    f32(state), i32(flags), f32(gamma), cur_stream());
+  return gamma;
+}
+
 // Sharded form of the Weiszfeld update: `dist2` holds the global squared
 // distances (multi-GPU d-sharding: all-reduced over RCCL). Accumulates
 // ||dz||^2 into `shift` (callers poll it every few iterations — no
@@ -682,6 +729,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::kw_only(), py::arg("cols"));
   m.def("krum_select", &krum_select, py::arg("G"), py::arg("f"), py::arg("q"),
         py::arg("iterative") = false);
+  m.def("krum_select", &agr_search,
+        "aggregator-tailored attack search (K14): flags, or gamma",
+        py::arg("G"), py::arg("f"), py::arg("q"), py::kw_only(),
+        py::arg("stats"), py::arg("rule"), py::arg("gammas") = c10::nullopt);
   m.def("caf_matvec", &caf_matvec);
   m.def("caf_colsum", &caf_colsum, py::arg("X"), py::arg("a"),
         py::arg("mu") = c10::nullopt, py::arg("scale") = c10::nullopt);

@@ -167,6 +167,31 @@ void launch_krum_select(const float* G, int n, int f, int q, int* out_idx,
 constexpr int KRUM_ITER_MAX_N = 128;
 void launch_krum_select_iter(const float* G, int n, int f, int q,
                              int* out_idx, hipStream_t stream);
+// Aggregator-tailored attack search: n honest rows (their f32 Gram G and the
+// 2n + 1 Min-Max statistics of launch_attack_stats), f >= 1 copies of
+// m(gamma) = mu + gamma p appended, the rule run on the n + f rows with
+// parameter f. rule AGR_RULE_KRUM: Krum / Multi-Krum with q winners;
+// AGR_RULE_BULYAN: the iterated selection above (q unused). One workgroup
+// per trial gamma. Needs n >= 2, f <= n, n + f <= KRUM_ITER_MAX_N, and
+// n >= 3f + 3 for Bulyan.
+constexpr int AGR_RULE_KRUM = 0;
+constexpr int AGR_RULE_BULYAN = 1;
+// flags[k] = 1 where gammas[k] is feasible, k < B.
+void launch_agr_flags(const float* G, const float* stats, int n, int f, int q,
+                      int rule, const float* gammas, int B, int* flags,
+                      hipStream_t stream);
+// gamma_out[0] = the feasible end of a bracket <= 2^-16 (relative) wide around
+// the upper end of the feasible interval that starts at gamma = 0: a
+// geometric grid, two linear grids, a one-wave finish. state
+// (AGR_STATE_FLOATS) and flags (AGR_GEO_POINTS + 2 AGR_LIN_POINTS) are
+// scratch. Bitwise repeatable; no host sync.
+constexpr int AGR_GEO_POINTS = 42;   // 0, then gamma0 2^-20 .. gamma0 2^20
+constexpr int AGR_LIN_POINTS = 256;  // gap / 257 per pass: 2 / 257^2 < 2^-15,
+                                     // 1 / 257^2 < 2^-16 of the lower end
+constexpr int AGR_STATE_FLOATS = 6;
+void launch_agr_search(const float* G, const float* stats, int n, int f, int q,
+                       int rule, float* state, int* flags, float* gamma_out,
+                       hipStream_t stream);
 void launch_smea_select(const float* G, const int* combos, int n, int m, int C,
                         unsigned long long* best, hipStream_t stream);
 void launch_mda_pass1(const float* D2, const int* prefixes, int P, int n,

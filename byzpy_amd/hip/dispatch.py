@@ -800,6 +800,160 @@ def min_sum(X: torch.Tensor, perturbation: str = "std") -> torch.Tensor:
     return torch.addcmul(mu, min_sum_gamma(a, c), p).to(X.dtype)
 
 
+# Aggregator-tailored attacks (Shejwalkar & Houmansadr 2021): f copies of
+# m = mu + gamma p with the largest gamma for which Krum / Multi-Krum / Bulyan,
+# run with parameter f on the n honest rows followed by the copies, still
+# selects them. Honest-honest distances come off the honest Gram, honest-
+# malicious ones are e_i(gamma) = max(a_i + 2 gamma b_i + gamma^2 c, 0),
+# malicious-malicious ones are 0: the search never touches X. It is a grid
+# search: gamma = 0 and gamma0 2^-20 .. gamma0 2^20 (gamma0 = sqrt(max a / c),
+# the Min-Sum value), then two linear grids of 256 interior points inside the
+# gap below the first infeasible point, which leaves a bracket 1 / 257^2 <
+# 2^-16 of its lower end wide; that (feasible) lower end is the answer.
+# ops/functional.py keeps its own text (explicit attacked matrix, bisection).
+
+# Row cap n + f of krum_select(G, f, q, stats=, rule=) (KRUM_ITER_MAX_N).
+AGR_MAX_N = 128
+_AGR_RULE_CODES = {"krum": 0, "multi-krum": 0, "bulyan": 1}
+_AGR_GEO_POINTS = 42
+_AGR_LIN_POINTS = 256
+
+
+def agr_krum_scores(
+    G: torch.Tensor,
+    a: torch.Tensor,
+    b: torch.Tensor,
+    c: torch.Tensor,
+    f: int,
+    gammas: torch.Tensor,
+):
+    """Krum scores (parameter f) of the attacked set at each of B trial
+    gammas, from the honest Gram and the statistics alone: (honest (B, n),
+    malicious (B,)). An honest row sums the n - 1 smallest of its n - 1 honest
+    distances and f copies of e_i; a malicious row f - 1 zeros and the n - f
+    smallest of e. Any device and float dtype, no host sync."""
+    n = G.shape[0]
+    B = gammas.numel()
+    inf = float("inf")
+    D2 = sq_dists_from_gram(G)
+    D2 = torch.where(torch.isfinite(D2), D2, torch.full_like(D2, inf))
+    D2.fill_diagonal_(inf)
+    g = gammas.reshape(B, 1)
+    e = a[None, :] + 2.0 * g * b[None, :] + g * g * c
+    e = torch.where(torch.isfinite(e), e.clamp_min(0.0), torch.full_like(e, inf))
+    aug = torch.cat(
+        [D2[None, :, :].expand(B, n, n), e[:, :, None].expand(B, n, f)], dim=2
+    )
+    honest = aug.sort(dim=2).values[:, :, : n - 1].sum(dim=2)
+    malicious = e.sort(dim=1).values[:, : n - f].sum(dim=1)
+    return honest, malicious
+
+
+def _agr_krum_flags(G, a, b, c, f: int, q: int, gammas: torch.Tensor):
+    """bool (B,): Krum / Multi-Krum with q winners still selects the
+    malicious rows — at most max(q - f, 0) honest rows score no worse than a
+    malicious one. Anything non-finite is infeasible."""
+    honest, malicious = agr_krum_scores(G, a, b, c, f, gammas)
+    ok = torch.isfinite(a).all() & torch.isfinite(b).all() & torch.isfinite(c)
+    beaten = (~(honest > malicious[:, None])).sum(dim=1)
+    return (beaten <= max(q - f, 0)) & ok & torch.isfinite(gammas)
+
+
+def _agr_gamma_torch(G, a, b, c, f: int, q: int) -> torch.Tensor:
+    """The device kernel's grid schedule as torch ops batched over the grid,
+    Krum / Multi-Krum only: any device, no host sync."""
+    dev, dt = a.device, a.dtype
+    zero = torch.zeros((), device=dev, dtype=dt)
+
+    def first_infeasible(flags):
+        B = flags.numel()
+        k = torch.arange(B, device=dev)
+        return torch.where(flags, torch.full_like(k, B), k).min()
+
+    def at(pts, k):  # pts[k] for a 0-dim index tensor, without a host sync
+        return pts.index_select(0, k.clamp(0, pts.numel() - 1).reshape(1)).reshape(())
+
+    BG, BL = _AGR_GEO_POINTS, _AGR_LIN_POINTS
+    gamma0 = torch.where(
+        c > 0, torch.sqrt(a.max().clamp_min(0.0) / torch.where(c > 0, c, 1.0)), zero
+    )
+    pts = gamma0 * torch.cat(
+        [zero[None], 2.0 ** torch.arange(-20, 21, device=dev, dtype=dt)]
+    )
+    j = first_infeasible(_agr_krum_flags(G, a, b, c, f, q, pts))
+    lo = torch.where(j <= 1, zero, at(pts, j - 1))  # j = BG: the top, twice
+    hi = torch.where(j <= 1, zero, at(pts, j))
+    frac = torch.arange(1, BL + 1, device=dev, dtype=dt) / (BL + 1)
+    for _ in range(2):
+        pts = lo + (hi - lo) * frac
+        j = first_infeasible(_agr_krum_flags(G, a, b, c, f, q, pts))
+        lo, hi = (
+            torch.where(j == 0, lo, at(pts, j - 1)),
+            torch.where(j == BL, hi, at(pts, j)),
+        )
+    return lo
+
+
+def _agr_fused(G: torch.Tensor, f: int) -> bool:
+    return _gpu(G) and G.dtype == torch.float32 and G.shape[0] + f <= AGR_MAX_N
+
+
+def agr_tailored_gamma(
+    G: torch.Tensor,
+    a: torch.Tensor,
+    b: torch.Tensor,
+    c: torch.Tensor,
+    f: int,
+    agr: str,
+    q: Optional[int] = None,
+) -> torch.Tensor:
+    """0-dim gamma of the tailored attack from the honest Gram (n, n) and the
+    statistics a (n,), b (n,), c () of ``attack_stats``: the feasible end of a
+    bracket at most 2^-16 (relative) wide around the largest feasible gamma;
+    0 when gamma = 0 is infeasible, c = 0 or a statistic is not finite. On
+    device to n + f <= AGR_MAX_N: three grid launches and a finish, no host
+    sync. Past that, and on CPU, Krum / Multi-Krum take the same schedule as
+    batched torch ops; Bulyan has the device kernel and the functional path
+    (``agr_tailored``) only. ``q`` defaults to n for Multi-Krum."""
+    n = G.shape[0]
+    q = F.agr_check(n, int(f), agr, q)
+    if _agr_fused(G, f):
+        stats = torch.cat([a.reshape(-1), b.reshape(-1), c.reshape(1)]).float()
+        return _hip.require().krum_select(
+            G.contiguous(), int(f), int(q), stats=stats.contiguous(),
+            rule=_AGR_RULE_CODES[agr],
+        )
+    if agr == "bulyan":
+        raise ValueError(
+            "the statistics form of the Bulyan search runs on the device "
+            f"kernel only (f32 device Gram, n + f <= {AGR_MAX_N})"
+        )
+    return _agr_gamma_torch(G, a, b, c, int(f), q)
+
+
+def agr_tailored(
+    X: torch.Tensor,
+    f: int,
+    agr: str = "multi-krum",
+    q: Optional[int] = None,
+    perturbation: str = "std",
+) -> torch.Tensor:
+    """Aggregator-tailored attack vector m = mu + gamma p against ``agr`` in
+    "krum" | "multi-krum" | "bulyan" run with f Byzantine rows on the n honest
+    rows of X plus f copies of m. On device: the statistics pass, the MFMA
+    Gram, the grid search on those O(n^2) numbers, one addcmul — no host sync,
+    capturable into a hipGraph. CPU tensors, and Bulyan past n + f =
+    AGR_MAX_N, take the functional path."""
+    _perturb_code(perturbation)
+    n = X.shape[0]
+    F.agr_check(n, int(f), agr, q)
+    if not _attack_device(X) or (agr == "bulyan" and n + f > AGR_MAX_N):
+        return F.agr_tailored(X, int(f), agr, q, perturbation)
+    mu, p, a, b, c = attack_stats(X, perturbation)
+    gamma = agr_tailored_gamma(gram(X), a, b, c, f, agr, q)
+    return torch.addcmul(mu, gamma, p).to(X.dtype)
+
+
 # -- remaining ops: torch composition on either device ----------------------
 
 

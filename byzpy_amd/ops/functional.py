@@ -734,3 +734,104 @@ def min_sum(honest: torch.Tensor, perturbation: str = "std") -> torch.Tensor:
     mu, p = attack_perturbation(honest, perturbation)
     gamma = min_sum_gamma(honest, perturbation)
     return (mu + gamma * p).to(honest.dtype)
+
+
+# Aggregator-tailored attacks (Shejwalkar & Houmansadr, NDSS 2021, section
+# IV-B): the adversary knows the server's rule and sends f copies of
+# m = mu + gamma * p with the largest gamma for which the rule still selects
+# them. The oracle's own text: the explicit (n + f, d) attacked matrix, the
+# existing Krum scores / Bulyan selection run on it, gamma by bisection. The
+# device path (hip/dispatch.py) works on the Gram and the quadratic
+# a_i + 2 gamma b_i + gamma^2 c instead.
+
+AGR_RULES = ("krum", "multi-krum", "bulyan")
+
+
+def agr_check(n: int, f: int, agr: str, q: Optional[int] = None) -> int:
+    """Validate the arguments of a tailored attack on n honest rows; returns
+    the winner count q (1 for Krum, n by default for Multi-Krum, unused by
+    Bulyan)."""
+    if agr not in AGR_RULES:
+        raise ValueError(f"agr must be one of {AGR_RULES}, got {agr!r}")
+    if f < 1:
+        raise ValueError(f"a tailored attack needs f >= 1, got f={f}")
+    if agr == "bulyan":
+        if n < 3 * f + 3:
+            raise ValueError(
+                f"Bulyan needs n + f >= 4f + 3, got n={n} honest rows, f={f}"
+            )
+        return n - f
+    if n < 2 or f > n:
+        raise ValueError(f"Krum needs n >= 2 and f <= n, got n={n}, f={f}")
+    if agr == "krum":
+        return 1
+    q = n if q is None else int(q)
+    if q < 1 or q > n + f:
+        raise ValueError(f"need 1 <= q <= n + f, got q={q}, n={n}, f={f}")
+    return q
+
+
+def _agr_attacked(honest: torch.Tensor, gamma: float, f: int, perturbation: str):
+    """cat(honest, f copies of mu + gamma p) in f64."""
+    mu, p = attack_perturbation(honest, perturbation)
+    m = mu + float(gamma) * p
+    return torch.cat([honest.double(), m[None, :].expand(f, -1)], dim=0)
+
+
+def agr_feasible(
+    honest: torch.Tensor,
+    gamma: float,
+    f: int,
+    agr: str,
+    q: Optional[int] = None,
+    perturbation: str = "std",
+) -> bool:
+    """Whether the rule, run with parameter f on the n honest rows followed
+    by f copies of mu + gamma p, selects the malicious rows: all f of them
+    for Bulyan; for Krum / Multi-Krum at most max(q - f, 0) honest rows score
+    no worse than a malicious one (ties go to the honest, smaller, index).
+    Anything NaN is infeasible."""
+    n = honest.shape[0]
+    q = agr_check(n, f, agr, q)
+    A = _agr_attacked(honest, gamma, f, perturbation)
+    if not bool(torch.isfinite(A).all()):
+        return False
+    if agr == "bulyan":
+        picks = bulyan_select(A, f)
+        return int((picks >= n).sum()) == f
+    scores = multi_krum_scores(A, f)
+    if bool(torch.isnan(scores).any()):
+        return False
+    s_m = scores[n:].max()
+    return int((scores[:n] <= s_m).sum()) <= max(q - f, 0)
+
+
+def agr_tailored_gamma(
+    honest: torch.Tensor,
+    f: int,
+    agr: str,
+    q: Optional[int] = None,
+    perturbation: str = "std",
+) -> float:
+    """Upper end of the feasible interval that starts at gamma = 0; 0 when
+    gamma = 0 is already infeasible or the perturbation vanishes."""
+    agr_check(honest.shape[0], f, agr, q)
+    _, p = attack_perturbation(honest, perturbation)
+    c = float((p * p).sum())
+    if c == 0.0 or not math.isfinite(c):
+        return 0.0
+    return _largest_feasible(
+        lambda g: agr_feasible(honest, g, f, agr, q, perturbation)
+    )
+
+
+def agr_tailored(
+    honest: torch.Tensor,
+    f: int,
+    agr: str = "multi-krum",
+    q: Optional[int] = None,
+    perturbation: str = "std",
+) -> torch.Tensor:
+    mu, p = attack_perturbation(honest, perturbation)
+    gamma = agr_tailored_gamma(honest, f, agr, q, perturbation)
+    return (mu + gamma * p).to(honest.dtype)
