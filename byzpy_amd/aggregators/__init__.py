@@ -5,6 +5,8 @@ from byzpy_amd.aggregators.coordinate_wise import (
     MeanOfMedians,
 )
 from byzpy_amd.aggregators.geometric_wise import (
+    AFA,
+    AFAReputation,
     Bulyan,
     DnC,
     GeometricMedian,
@@ -29,6 +31,8 @@ __all__ = [
     "Krum",
     "Bulyan",
     "DnC",
+    "AFA",
+    "AFAReputation",
     "GeometricMedian",
     "MinimumDiameterAveraging",
     "MoNNA",

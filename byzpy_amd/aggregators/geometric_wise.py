@@ -8,6 +8,7 @@ Gram runs on the MFMA split-K kernel (K4); selection/scoring on small
 from __future__ import annotations
 
 import itertools
+import math
 from typing import Any, List, Sequence
 
 import torch
@@ -252,6 +253,147 @@ class DnC(Aggregator):
             return to_like(D.mean_rows_counted(X, idx, count), like)
         finally:
             self._cleanup(handles)
+
+
+class AFA(Aggregator):
+    """Adaptive Federated Averaging (Muñoz-González, Co, Lupu 2019), one
+    round of its Algorithm 1: pass after pass, drop the rows whose cosine to
+    the weighted mean of the rows still alive lies more than xi standard
+    deviations past the median, on the side the mean lies (xi grows by
+    delta_xi after every pass that dropped a row), then return the weighted
+    mean of the survivors; zeros when none survives (skip the round).
+
+    ``weights`` (n,) >= 0, default all ones, may be replaced between calls
+    (``agg.weights = ...``); AFAReputation keeps the paper's cross-round
+    state and produces them. A non-finite row or one of weight 0 is never
+    kept.
+
+    GPU: MFMA Gram, one selection launch, counted gather-mean — no host sync
+    up to 128 rows. CPU pools: row-chunked Gram."""
+
+    name = "afa"
+    supports_subtasks = True
+    max_subtasks_inflight = 0
+
+    def __init__(
+        self,
+        xi: float = 2.0,
+        delta_xi: float = 0.5,
+        *,
+        weights: "torch.Tensor | Sequence[float] | None" = None,
+        chunk_size: int = 32,
+    ) -> None:
+        F._afa_check(xi, delta_xi)
+        self.xi, self.delta_xi = float(xi), float(delta_xi)
+        self.weights = weights
+        self.chunk_size = int(chunk_size)
+
+    def _aggregate(self, X: torch.Tensor) -> torch.Tensor:
+        return D.afa(X, self.weights, self.xi, self.delta_xi)
+
+    def create_subtasks(self, ctx: OpContext, **inputs: Any) -> Sequence[SubTask]:
+        gradients = inputs[self.input_key]
+        ref, X, like, handles = self._matrix_ref(ctx, gradients)
+        if X.is_cuda:
+            return []
+        n = X.shape[0]
+        try:
+            F._afa_weights(self.weights, n)
+        except ValueError:
+            self._cleanup(handles)
+            raise
+        ctx.metadata["_op_pending"] = (X, like, handles)
+        chunk = max(1, min(self.chunk_size, n))
+        return [
+            SubTask(fn=SF.gram_row_chunk, args=(ref, lo, hi), name=f"gram[{lo}:{hi}]")
+            for lo, hi in chunk_ranges(n, chunk)
+        ]
+
+    def reduce_subtasks(self, ctx: OpContext, results: List[Any], **inputs: Any) -> Any:
+        X, like, handles = ctx.metadata.pop("_op_pending")
+        try:
+            G = torch.cat(results, dim=0)
+            idx, count = D.afa_select_from_gram(
+                G, self.weights, self.xi, self.delta_xi
+            )
+            w = None
+            if self.weights is not None:
+                w = F._afa_weights(self.weights, X.shape[0])
+            return to_like(D.mean_rows_counted(X, idx, count, weights=w), like)
+        finally:
+            self._cleanup(handles)
+
+
+class AFAReputation:
+    """The cross-round state of AFA: a Beta(alpha, beta) belief per client
+    that it sends good updates. ``update(good_mask)`` adds 1 to alpha for the
+    clients the round kept and to beta for those it dropped; a client is
+    ``blocked`` once P[p < 0.5] = I_0.5(alpha, beta) >= block_at, and is
+    never updated again. ``weights(sizes)`` = alpha / (alpha + beta) * sizes,
+    0 where blocked: what AFA takes as ``weights``.
+
+    alpha0, beta0 are positive integers, so the Beta CDF at 0.5 is the
+    finite binomial sum sum_{j=alpha}^{N} C(N, j) 2^-N with
+    N = alpha + beta - 1, computed exactly in integers."""
+
+    def __init__(
+        self, n: int, alpha0: float = 3.0, beta0: float = 3.0, block_at: float = 0.95
+    ) -> None:
+        if n < 1:
+            raise ValueError("n must be >= 1")
+        if alpha0 != int(alpha0) or beta0 != int(beta0) or alpha0 < 1 or beta0 < 1:
+            raise ValueError("alpha0 and beta0 must be integers >= 1")
+        if not 0.0 < block_at <= 1.0:
+            raise ValueError("block_at must lie in (0, 1]")
+        self.alpha = [int(alpha0)] * int(n)
+        self.beta = [int(beta0)] * int(n)
+        self.block_at = float(block_at)
+        self._blocked = [False] * int(n)
+        self._refresh()
+
+    @staticmethod
+    def cdf_half(alpha: int, beta: int) -> float:
+        """I_0.5(alpha, beta) for integers alpha, beta >= 1."""
+        N = alpha + beta - 1
+        return sum(math.comb(N, j) for j in range(alpha, N + 1)) / 2**N
+
+    def _refresh(self) -> None:
+        for i, (a, b) in enumerate(zip(self.alpha, self.beta)):
+            if not self._blocked[i] and self.cdf_half(a, b) >= self.block_at:
+                self._blocked[i] = True
+
+    @property
+    def blocked(self) -> torch.Tensor:
+        return torch.tensor(self._blocked, dtype=torch.bool)
+
+    def update(self, good_mask) -> None:
+        good = torch.as_tensor(good_mask).detach().cpu().flatten().tolist()
+        if len(good) != len(self.alpha):
+            raise ValueError(
+                f"good_mask: expected {len(self.alpha)} entries, got {len(good)}"
+            )
+        for i, g in enumerate(good):
+            if self._blocked[i]:
+                continue
+            if g:
+                self.alpha[i] += 1
+            else:
+                self.beta[i] += 1
+        self._refresh()
+
+    def weights(self, sizes=None) -> torch.Tensor:
+        p = torch.tensor(
+            [a / (a + b) for a, b in zip(self.alpha, self.beta)],
+            dtype=torch.float32,
+        )
+        if sizes is not None:
+            sz = torch.as_tensor(sizes, dtype=torch.float32).flatten()
+            if sz.numel() != p.numel():
+                raise ValueError(
+                    f"sizes: expected {p.numel()} entries, got {sz.numel()}"
+                )
+            p = p * sz
+        return p.masked_fill(self.blocked, 0.0)
 
 
 class GeometricMedian(Aggregator):

@@ -5,6 +5,7 @@
 #include <c10/hip/HIPStream.h>
 
 #include <climits>
+#include <cmath>
 #include <vector>
 
 #include "launchers.h"
@@ -266,6 +267,37 @@ torch::Tensor mean_rows_counted(torch::Tensor X, torch::Tensor idx,
     using T = TAG_T(tag);
     launch_mean_rows_counted<T>(ptr<T>(X), i32(idx), k, i32(count),
                                 ptr<T>(out), d, cur_stream());
+  });
+  return out;
+}
+
+// mean_rows(X, idx, count=c, weights=w): the weighted mean
+// sum_k w[idx[k]] x[idx[k]] / sum_k w[idx[k]] over k < c, w an f32 device
+// vector with one weight per row of X; zeros when c or the weight sum is 0.
+torch::Tensor mean_rows_counted_weighted(torch::Tensor X, torch::Tensor idx,
+                                         torch::Tensor count,
+                                         torch::Tensor weights) {
+  check_matrix(X);
+  check_i32(idx, 1, "idx");
+  TORCH_CHECK(idx.numel() >= 1 && idx.numel() <= MAX_N_LDS,
+              "mean_rows(weights=) supports 1 <= len(idx) <= ", MAX_N_LDS,
+              ", got ", idx.numel());
+  TORCH_CHECK(count.is_cuda() && count.scalar_type() == torch::kInt32 &&
+                  count.numel() == 1,
+              "count: expected an int32 device scalar");
+  TORCH_CHECK(X.size(0) >= 1 && X.size(0) <= INT_MAX, "bad row count");
+  check_f32_vector(weights, X.size(0), "weights");
+  TORCH_CHECK(idx.device() == X.device() && count.device() == X.device() &&
+                  weights.device() == X.device(),
+              "idx, count, weights: expected X's device");
+  const long d = (long)X.size(1);
+  const int k = (int)idx.numel();
+  auto out = torch::empty({d}, X.options());
+  by_dtype(X, [&](auto tag) {
+    using T = TAG_T(tag);
+    launch_mean_rows_counted_weighted<T>(ptr<T>(X), i32(idx), k, i32(count),
+                                         f32(weights), (int)X.size(0),
+                                         ptr<T>(out), d, cur_stream());
   });
   return out;
 }
@@ -601,6 +633,33 @@ std::vector<torch::Tensor> dnc_select(torch::Tensor Gc3, torch::Tensor bad,
   return {idx, count};
 }
 
+// smea_select(G, weights=w, xi=, delta_xi=): the AFA selection (subsets.hip)
+// on the f32 Gram G (n, n) with row weights w (n,), one launch for the whole
+// data-dependent loop. Returns (idx int32 (n,), count int32 (), rounds int32
+// ()): idx[:count] are the ascending indices still alive, the rest is
+// padding; rounds is the number of loop passes. No host sync.
+std::vector<torch::Tensor> afa_select(torch::Tensor G, torch::Tensor weights,
+                                      double xi, double delta_xi) {
+  check_gram(G, "G");
+  const int64_t n = G.size(0);
+  TORCH_CHECK(n >= 1 && n <= AFA_MAX_N, "smea_select(G, weights=) supports ",
+              "1 <= n <= ", AFA_MAX_N, ", got ", n);
+  TORCH_CHECK(weights.dim() == 1, "weights: expected one dimension, got ",
+              weights.dim());
+  check_f32_vector(weights, n, "weights");
+  TORCH_CHECK(weights.device() == G.device(), "weights: expected G's device");
+  TORCH_CHECK(xi >= 0.0 && xi < INFINITY, "xi: expected a finite value >= 0, ",
+              "got ", xi);
+  TORCH_CHECK(delta_xi >= 0.0 && delta_xi < INFINITY,
+              "delta_xi: expected a finite value >= 0, got ", delta_xi);
+  auto idx = torch::empty({n}, i32_like(G));
+  auto count = torch::empty({}, i32_like(G));
+  auto rounds = torch::empty({}, i32_like(G));
+  launch_afa_select(f32(G), f32(weights), (int)n, xi, delta_xi, i32(idx),
+                    i32(count), i32(rounds), cur_stream());
+  return {idx, count, rounds};
+}
+
 // MDA two-pass device search: returns (found[npairs], subsets[npairs, m]);
 // the first found prefix (pair-lex order) holds the lex-smallest optimal
 // subset. No host sync anywhere.
@@ -721,6 +780,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mean_rows", &mean_rows_counted,
         "mean of rows idx[:count], count an int32 device scalar (K15)",
         py::arg("X"), py::arg("idx"), py::kw_only(), py::arg("count"));
+  m.def("mean_rows", &mean_rows_counted_weighted,
+        "weighted mean of rows idx[:count], one f32 weight per row of X (K16)",
+        py::arg("X"), py::arg("idx"), py::kw_only(), py::arg("count"),
+        py::arg("weights"));
   m.def("group_mean_rows", &group_mean_rows);
   m.def("bucket_mean", &bucket_mean);
   m.def("gram", &gram);
@@ -747,6 +810,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("smea_select", &dnc_select,
         "DnC spectral selection (K15): (idx, count)", py::arg("Gc3"),
         py::arg("bad"), py::arg("keep"));
+  m.def("smea_select", &afa_select,
+        "AFA selection (K16): (idx, count, rounds)", py::arg("G"),
+        py::kw_only(), py::arg("weights"), py::arg("xi"), py::arg("delta_xi"));
   m.def("little_fused", &little_fused, "fused Little attack (K14)");
   m.def("little_fused", &little_fused_stats,
         "Min-Max / Min-Sum statistics pass (K14): (mu, p, stats)",

@@ -92,6 +92,21 @@ void launch_dnc_select(const float* Gc, const int* bad, int niters, int n,
                        int keep, int* kept, int* idx, int* count,
                        hipStream_t stream);
 
+// subsets.hip (K16, AFA). Row cap of the selection kernel: one thread per
+// (16-entry row segment, row) of the Gram.
+constexpr int AFA_MAX_N = 128;
+// The whole AFA loop on the f32 Gram G (n, n) with row weights w (n,), one
+// block: rows with a non-finite G_ii or a weight that is not a positive
+// finite number start dead; each pass drops the alive rows whose cosine to
+// the weighted mean of the alive rows lies past med -/+ xi sd (the side
+// chosen by mean < med), xi += delta_xi after a pass that dropped a row, and
+// the first pass that drops none ends it. idx receives the ascending alive
+// indices padded with 0 to n entries, count their number, rounds the number
+// of passes. 1 <= n <= AFA_MAX_N.
+void launch_afa_select(const float* G, const float* w, int n, double xi,
+                       double delta_xi, int* idx, int* count, int* rounds,
+                       hipStream_t stream);
+
 // rowops.hip
 template <typename T>
 void launch_row_sqnorms(const T* X, float* out, int n, long d,
@@ -111,6 +126,15 @@ template <typename T>
 void launch_mean_rows_counted(const T* X, const int* idx, int k,
                               const int* count, T* out, long d,
                               hipStream_t stream);
+// The same with row weights: sum_i w[idx[i]] x[idx[i]] / sum_i w[idx[i]] over
+// i < *count; zeros when the count or the weight sum is 0. X and w have
+// n_src rows (idx is clamped to them); k <= MAX_N_LDS (the weights are
+// staged in LDS).
+template <typename T>
+void launch_mean_rows_counted_weighted(const T* X, const int* idx, int k,
+                                       const int* count, const float* w,
+                                       int n_src, T* out, long d,
+                                       hipStream_t stream);
 template <typename T>
 void launch_group_mean_rows(const T* X, const int* idx, int g, int k, T* out,
                             long d, hipStream_t stream);

@@ -9,6 +9,8 @@
 //                                           gather_mean_kernel (both)
 //   mean_rows(count=)  the same over idx[:count], count read on the device
 //                                           gather_mean_counted_kernel
+//   mean_rows(count=, weights=)  the weighted mean over idx[:count]
+//                                           gather_wmean_counted_kernel
 //   bucket_mean        permuted segmented mean -> (nb,d) (Bucketing)
 //                                           bucket_mean_kernel
 //   weiszfeld_iter/_apply  w=1/max(dist,eps); z' = sum(w x)/sum(w); ||dz||^2
@@ -428,6 +430,34 @@ __global__ void gather_mean_counted_kernel(const T* __restrict__ X,
       [](int) { return 1.0f; }, [&](long, float acc) { return acc * inv; });
 }
 
+// Weighted counted variant (AFA): sum_i w[idx[i]] x[idx[i]] / sum_i w[idx[i]]
+// over i < count. Again a kernel of its own, so that the counted kernel
+// above keeps its instruction stream too. The cnt <= MAX_N_LDS weights are
+// staged once per block; a weight sum that is not positive reads no row and
+// writes zeros, like count 0.
+template <typename T, bool VEC>
+__global__ void gather_wmean_counted_kernel(const T* __restrict__ X,
+                                            const int* __restrict__ idx, int k,
+                                            const int* __restrict__ count,
+                                            const float* __restrict__ w,
+                                            int n_src, T* __restrict__ out,
+                                            long d) {
+  __shared__ float w_lds[MAX_N_LDS];
+  int cnt = min(max(*count, 0), min(k, MAX_N_LDS));
+  // idx comes from device memory: clamped to the n_src rows of X and w
+  const auto src = [&](int i) { return min(max(idx[i], 0), n_src - 1); };
+  const float den =
+      stage_weights(w_lds, cnt, blockDim.x, [&](int i) { return w[src(i)]; });
+  const bool ok = den > 0.0f && den < INFINITY;
+  if (!ok) cnt = 0;
+  const float inv = ok ? 1.0f / den : 0.0f;
+  const long start = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long stride = (long)gridDim.x * blockDim.x;
+  col_wsum<T, VEC>(
+      X, out, d, start, stride, 0, cnt, src, [&](int i) { return w_lds[i]; },
+      [&](long, float acc) { return acc * inv; });
+}
+
 template <typename T, bool VEC>
 __global__ void bucket_mean_kernel(const T* __restrict__ X,
                                    const int* __restrict__ perm, int n,
@@ -704,6 +734,19 @@ void launch_mean_rows_counted(const T* X, const int* idx, int k,
 }
 
 template <typename T>
+void launch_mean_rows_counted_weighted(const T* X, const int* idx, int k,
+                                       const int* count, const float* w,
+                                       int n_src, T* out, long d,
+                                       hipStream_t stream) {
+  by_vec<T>(d, [&](auto v) {
+    const long work = col_work<T, VEC_OF(v)>(d);
+    hipLaunchKernelGGL((gather_wmean_counted_kernel<T, VEC_OF(v)>),
+                       dim3(col_grid(work, BLOCK)), dim3(BLOCK), 0, stream, X,
+                       idx, k, count, w, n_src, out, d);
+  });
+}
+
+template <typename T>
 void launch_group_mean_rows(const T* X, const int* idx, int g, int k, T* out,
                             long d, hipStream_t stream) {
   by_vec<T>(d, [&](auto v) {
@@ -779,6 +822,7 @@ INSTANTIATE_LAUNCHER(launch_grouped_weiszfeld)
 INSTANTIATE_LAUNCHER(launch_row_scale)
 INSTANTIATE_LAUNCHER(launch_mean_rows)
 INSTANTIATE_LAUNCHER(launch_mean_rows_counted)
+INSTANTIATE_LAUNCHER(launch_mean_rows_counted_weighted)
 INSTANTIATE_LAUNCHER(launch_group_mean_rows)
 INSTANTIATE_LAUNCHER(launch_bucket_mean)
 INSTANTIATE_LAUNCHER(launch_weiszfeld_update)

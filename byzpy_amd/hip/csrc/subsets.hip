@@ -407,7 +407,210 @@ dnc_intersect_kernel(const int* __restrict__ kept, int niters, int n,
   }
 }
 
+// ---------------------------------------------------------------------------
+// AFA selection (K16)
+// ---------------------------------------------------------------------------
+
+// Adaptive Federated Averaging drops, pass after pass, the rows whose cosine
+// to the weighted mean g of the rows still alive is an outlier. With w masked
+// to the alive rows, u = G w and q = w^T G w give
+//   cos(x_i, g) = u_i / sqrt(G_ii q),
+// so the whole data-dependent loop runs on the (n, n) Gram in ONE block: the
+// loop ends on a block-wide "nothing removed" vote, no host in between.
+//
+// Thread (r, i) keeps G[i][16 r .. 16 r + 15] in registers for every pass
+// (the layout of dnc_scores_kernel, read by rows: G need not be symmetric).
+// A pass is 16 f64 FMAs per thread against the masked weights in LDS, then
+// one thread per row adds its <= 8 segment partials in segment order; q, the
+// mean and the two-pass variance are summed the same way, 16 terms per
+// segment and then the segments, always in index order. u, q, the cosines
+// and their statistics are f64: at n <= 128 that costs nothing, and the
+// decisions then differ from an f64 evaluation of the same Gram by rounding
+// of order 1e-16 only. No atomics anywhere: the same G bits give the same
+// output bits.
+//
+// Median by rank counting, rank_i = #{alive j : s_j < s_i or (s_j == s_i and
+// j < i)}: the ranks of the alive rows are a permutation of 0 .. m - 1, so
+// exactly one row writes each of the two middle values.
+
+constexpr int AFA_SEL_THREADS = 1024;
+constexpr int AFA_SEG = 16;  // Gram entries of one row per thread
+constexpr int AFA_MAX_SEGS = AFA_MAX_N / AFA_SEG;
+static_assert(AFA_MAX_SEGS * AFA_MAX_N <= AFA_SEL_THREADS, "one thread per (segment, row)");
+
+__global__ void __launch_bounds__(AFA_SEL_THREADS)
+afa_select_kernel(const float* __restrict__ G, const float* __restrict__ w,
+                  int n, double xi, double delta_xi, int* __restrict__ idx,
+                  int* __restrict__ count, int* __restrict__ rounds) {
+  __shared__ double part[AFA_MAX_SEGS][AFA_MAX_N];
+  __shared__ double wm[AFA_MAX_N];    // w_j where j is alive, else 0
+  __shared__ double diag[AFA_MAX_N];  // G_jj
+  __shared__ double s[AFA_MAX_N];     // u_j, then cos(x_j, g)
+  __shared__ double mid[2];           // the two middle cosines
+  __shared__ double seg[2][AFA_MAX_SEGS];  // segment sums
+  __shared__ int rpart[AFA_MAX_SEGS][AFA_MAX_N];  // segment rank counts
+  __shared__ int alive[AFA_MAX_N];
+  const int tid = threadIdx.x;
+  const int segs = (n + AFA_SEG - 1) / AFA_SEG;
+  const int i = tid % n, r = tid / n;
+  const bool active = r < segs;
+  const bool row = tid < n;  // this thread also owns row tid
+
+  // a non-finite entry belongs to a row that starts dead; as 0 it cannot
+  // turn 0 * inf into NaN in a live row's sum
+  float a[AFA_SEG];
+#pragma unroll
+  for (int m = 0; m < AFA_SEG; ++m) {
+    const int k = r * AFA_SEG + m;
+    float x = (active && k < n) ? G[(long)i * n + k] : 0.0f;
+    if (!(fabsf(x) < INFINITY)) x = 0.0f;
+    a[m] = x;
+  }
+  bool ok = false;
+  if (tid < AFA_MAX_N) {
+    const float g = row ? G[(long)tid * n + tid] : 0.0f;
+    const float wi = row ? w[tid] : 0.0f;
+    ok = row && fabsf(g) < INFINITY && wi > 0.0f && wi < INFINITY;
+    alive[tid] = ok ? 1 : 0;
+    diag[tid] = ok ? (double)g : 0.0;
+    wm[tid] = ok ? (double)wi : 0.0;
+    s[tid] = 0.0;  // entries past n stay 0: whole segments are summed
+  }
+  int m = __syncthreads_count(ok);  // alive rows; the same in every thread
+
+  // Nothing in a pass walks all n rows in one thread. Sums go in two levels,
+  // both in a fixed order: thread t < segs adds the 16 terms of segment t,
+  // then every row thread adds the <= 8 segment sums. Ranks likewise: thread
+  // (r, i) counts the rows of segment r that sort before row i.
+  const bool segsum = tid < segs;
+  int passes = 0;
+  for (int it = 0; it < n && m > 0; ++it) {
+    ++passes;
+    if (active) {
+      double p = 0.0;
+#pragma unroll
+      for (int t = 0; t < AFA_SEG; ++t)
+        p = fma((double)a[t], wm[r * AFA_SEG + t], p);  // wm is 0 past n
+      part[r][i] = p;
+    }
+    __syncthreads();
+    if (row) {
+      double u = 0.0;
+      for (int t = 0; t < segs; ++t) u += part[t][tid];
+      s[tid] = u;
+    }
+    __syncthreads();
+    if (segsum) {  // q = sum_j w_j u_j
+      double t = 0.0;
+#pragma unroll
+      for (int k = 0; k < AFA_SEG; ++k)
+        t += wm[tid * AFA_SEG + k] * s[tid * AFA_SEG + k];
+      seg[0][tid] = t;
+    }
+    __syncthreads();
+    if (row) {
+      double q = 0.0;
+      for (int t = 0; t < segs; ++t) q += seg[0][t];
+      const double gii = diag[tid];
+      s[tid] = (alive[tid] && gii > 0.0 && q > 0.0) ? s[tid] / sqrt(gii * q)
+                                                    : 0.0;
+    }
+    __syncthreads();
+    if (segsum) {  // the cosine of a dead row is stored as 0
+      double t = 0.0;
+#pragma unroll
+      for (int k = 0; k < AFA_SEG; ++k) t += s[tid * AFA_SEG + k];
+      seg[0][tid] = t;
+    }
+    __syncthreads();
+    double mean = 0.0;
+    if (row || segsum) {
+      for (int t = 0; t < segs; ++t) mean += seg[0][t];
+      mean /= (double)m;
+    }
+    if (segsum) {  // two-pass variance
+      double t = 0.0;
+#pragma unroll
+      for (int k = 0; k < AFA_SEG; ++k) {
+        const double dv = s[tid * AFA_SEG + k] - mean;
+        t += alive[tid * AFA_SEG + k] ? dv * dv : 0.0;
+      }
+      seg[1][tid] = t;
+    }
+    if (active) {
+      const double si = s[i];
+      int c = 0;
+#pragma unroll
+      for (int k = 0; k < AFA_SEG; ++k) {
+        const int j = r * AFA_SEG + k;
+        const double sj = s[j];
+        c += (alive[j] && (sj < si || (sj == si && j < i))) ? 1 : 0;
+      }
+      rpart[r][i] = c;
+    }
+    __syncthreads();
+    const bool mine = row && alive[tid];
+    double sd = 0.0;
+    if (mine) {
+      for (int t = 0; t < segs; ++t) sd += seg[1][t];
+      sd = sqrt(sd / (double)m);
+      const double si = s[tid];
+      int rank = 0;
+      for (int t = 0; t < segs; ++t) rank += rpart[t][tid];
+      if (rank == (m - 1) / 2) mid[0] = si;
+      if (rank == m / 2) mid[1] = si;
+    }
+    __syncthreads();
+    int rm = 0;
+    if (mine) {
+      const double med = 0.5 * (mid[0] + mid[1]);
+      const double si = s[tid];
+      rm = mean < med ? (si < med - xi * sd) : (si > med + xi * sd);
+    }
+    // the barrier also orders this pass's reads of alive / wm / mid before
+    // the writes below, and its count is the block-wide vote
+    const int removed = __syncthreads_count(rm);
+    if (removed == 0) break;
+    if (rm) {
+      alive[tid] = 0;
+      wm[tid] = 0.0;
+    }
+    m -= removed;
+    xi += delta_xi;
+    __syncthreads();
+  }
+
+  __syncthreads();
+  const int n8 = (n + 7) & ~7;  // alive is 0 past n
+  if (row) {
+    int before = 0;
+    for (int j0 = 0; j0 < n8; j0 += 8) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) before += j0 + k < tid ? alive[j0 + k] : 0;
+    }
+    if (alive[tid]) idx[before] = tid;
+    // the dead rows fill the tail in order, so every slot is written once
+    else idx[m + (tid - before)] = 0;
+    if (tid == 0) {
+      *count = m;
+      *rounds = passes;
+    }
+  }
+}
+
 }  // namespace
+
+void launch_afa_select(const float* G, const float* w, int n, double xi,
+                       double delta_xi, int* idx, int* count, int* rounds,
+                       hipStream_t stream) {
+  // one thread per (segment, row) in whole waves, and at least the AFA_MAX_N
+  // threads that clear the LDS vectors
+  const int segs = (n + AFA_SEG - 1) / AFA_SEG;
+  int threads = ((segs * n + 63) / 64) * 64;
+  if (threads < AFA_MAX_N) threads = AFA_MAX_N;
+  hipLaunchKernelGGL(afa_select_kernel, dim3(1), dim3(threads), 0, stream, G,
+                     w, n, xi, delta_xi, idx, count, rounds);
+}
 
 void launch_dnc_select(const float* Gc, const int* bad, int niters, int n,
                        int keep, int* kept, int* idx, int* count,

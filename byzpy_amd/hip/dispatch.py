@@ -2,8 +2,9 @@
 
 CPU tensors -> byzpy_amd.ops.functional (pure torch, the parity oracle).
 CUDA(ROCm) tensors -> hand-written gfx950 kernels in byzpy_amd/_hip_ops
-(SURVEY.md §2.7 kernel inventory K1-K14, plus K15 for DnC). Ops whose GPU
-path composes library GEMMs / batched eig (SMEA combos, attacks) run the functional
+(SURVEY.md §2.7 kernel inventory K1-K14, plus K15 for DnC and K16 for
+AFA). Ops whose GPU path composes
+library GEMMs / batched eig (SMEA combos, attacks) run the functional
 torch path on-device — rocBLAS library GEMMs are the sanctioned path for
 plain GEMM shapes. CAF runs on the fused K9 matvec/colsum kernel pair.
 """
@@ -287,20 +288,45 @@ def mean_rows(X: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     return X.float()[idx].mean(dim=0).to(X.dtype)
 
 
+# Longest idx of mean_rows(count=, weights=): the kernel stages the weights in
+# LDS (MAX_N_LDS in csrc/launchers.h).
+MEAN_ROWS_WEIGHTED_MAX_K = 1024
+
+
 def mean_rows_counted(
-    X: torch.Tensor, idx: torch.Tensor, count: torch.Tensor
+    X: torch.Tensor,
+    idx: torch.Tensor,
+    count: torch.Tensor,
+    weights: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """Mean of rows idx[:count] with ``count`` an int32 scalar tensor that a
     device X reads on the device (no host sync); zeros when it is 0. Bitwise
-    ``mean_rows(X, idx[:count])`` otherwise."""
-    if _gpu(X):
+    ``mean_rows(X, idx[:count])`` otherwise. With ``weights`` (one per row of
+    X) the weighted mean sum_k w[idx[k]] x[idx[k]] / sum_k w[idx[k]], f32
+    accumulation, zeros when the weight sum is 0; a kernel of its own on
+    device to MEAN_ROWS_WEIGHTED_MAX_K indices, torch ops (which sync) past
+    that and on CPU."""
+    if weights is None:
+        if _gpu(X):
+            return _hip.require().mean_rows(
+                X.contiguous(), idx.to(torch.int32), count=count.to(torch.int32)
+            )
+        k = int(count)
+        if k == 0:
+            return torch.zeros_like(X[0])
+        return X.float()[idx[:k].long()].mean(dim=0).to(X.dtype)
+    if _gpu(X) and 1 <= idx.numel() <= MEAN_ROWS_WEIGHTED_MAX_K:
+        w = weights.to(device=X.device, dtype=torch.float32).contiguous()
         return _hip.require().mean_rows(
-            X.contiguous(), idx.to(torch.int32), count=count.to(torch.int32)
+            X.contiguous(), idx.to(torch.int32).contiguous(),
+            count=count.to(torch.int32), weights=w,
         )
-    k = int(count)
-    if k == 0:
+    rows = idx[: int(count)].long()
+    w = weights.to(device=X.device, dtype=torch.float32)[rows]
+    den = w.sum()
+    if rows.numel() == 0 or not float(den) > 0.0:
         return torch.zeros_like(X[0])
-    return X.float()[idx[:k].long()].mean(dim=0).to(X.dtype)
+    return ((w[:, None] * X.float()[rows]).sum(dim=0) / den).to(X.dtype)
 
 
 # -- DnC (K15) ---------------------------------------------------------------
@@ -420,6 +446,129 @@ def dnc(
         return F.dnc(X, f, coords, c)
     idx, count = _dnc_idx(X, f, coords, c)
     return mean_rows_counted(X, idx, count)
+
+
+# -- AFA (K16) ---------------------------------------------------------------
+#
+# Adaptive Federated Averaging (Muñoz-González, Co, Lupu 2019): drop, pass
+# after pass, the rows whose cosine to the weighted mean g of the rows still
+# alive is an outlier, then average the rest. With w masked to the alive rows,
+# u = G w and q = w^T G w give cos(x_i, g) = u_i / sqrt(G_ii q): the whole
+# loop lives on the (n, n) Gram and nothing d-sized is formed before the final
+# mean. ops/functional.py keeps its own text (explicit mean vector and norms)
+# as the oracle.
+
+# Row cap of smea_select(G, weights=, xi=, delta_xi=) (AFA_MAX_N in
+# csrc/launchers.h).
+AFA_MAX_N = 128
+
+
+def _afa_device_weights(weights, n: int, device) -> torch.Tensor:
+    """The (n,) f32 weight vector on ``device``. Host weights are checked
+    (``ValueError``); a device tensor is only checked for its length, so that
+    nothing syncs: there a weight that is negative, NaN or inf marks its row
+    dead."""
+    if weights is None:
+        return torch.ones(n, dtype=torch.float32, device=device)
+    if isinstance(weights, torch.Tensor) and weights.is_cuda:
+        if weights.numel() != n:
+            raise ValueError(f"weights: expected {n} entries, got {weights.numel()}")
+        return weights.detach().flatten().to(device=device, dtype=torch.float32)
+    return F._afa_weights(weights, n).to(device=device, dtype=torch.float32)
+
+
+def _afa_select_torch(G: torch.Tensor, w: torch.Tensor, xi: float, delta_xi: float):
+    """The AFA loop as f64 torch ops on the Gram, any device: (idx, count,
+    rounds). Every pass syncs the host (the loop ends on the data)."""
+    n = G.shape[0]
+    Gd, wd = G.double(), w.double()
+    diag = Gd.diagonal()
+    alive = torch.isfinite(diag) & torch.isfinite(wd) & (wd > 0)
+    Gz = torch.where(torch.isfinite(Gd), Gd, torch.zeros_like(Gd))
+    zero = torch.zeros_like(wd)
+    xi = float(xi)
+    rounds = 0
+    for _ in range(n):
+        m = int(alive.sum())
+        if m == 0:
+            break
+        rounds += 1
+        wm = torch.where(alive, wd, zero)
+        u = Gz @ wm
+        q = wm @ u
+        ok = alive & (diag > 0) & (q > 0)
+        s = torch.where(ok, u / (diag * q).clamp_min(1e-300).sqrt(), zero)
+        sa = s[alive]
+        mean = sa.mean()
+        srt = torch.sort(sa).values
+        med = 0.5 * (srt[(m - 1) // 2] + srt[m // 2])
+        sd = ((sa - mean) ** 2).mean().sqrt()
+        if bool(mean < med):
+            removed = alive & (s < med - xi * sd)
+        else:
+            removed = alive & (s > med + xi * sd)
+        if not bool(removed.any()):
+            break
+        alive = alive & ~removed
+        xi += float(delta_xi)
+    idx = torch.argsort((~alive).to(torch.int8), stable=True).to(torch.int32)
+    idx = torch.where(alive[idx.long()], idx, torch.zeros_like(idx))
+    return idx, alive.sum().to(torch.int32), rounds
+
+
+def afa_select_from_gram(
+    G: torch.Tensor, weights=None, xi: float = 2.0, delta_xi: float = 0.5
+):
+    """(idx int32 (n,), count int32 ()) of AFA's good set from the Gram
+    G = X X^T: idx[:count] are the ascending indices of the rows still alive
+    when a pass drops nothing (see ``functional.afa_select`` for the rule),
+    the rest of idx is padding 0. Rows with a non-finite G_ii or a weight
+    that is not positive start dead. One fused launch on device for f32 Grams
+    to AFA_MAX_N rows, no host sync; otherwise the same passes as f64 torch
+    ops on G's device, which sync the host once per pass."""
+    F._afa_check(xi, delta_xi)
+    n = G.shape[0]
+    w = _afa_device_weights(weights, n, G.device)
+    if _gpu(G) and 1 <= n <= AFA_MAX_N and G.dtype == torch.float32:
+        idx, count, _ = _hip.require().smea_select(
+            G.contiguous(), weights=w.contiguous(), xi=float(xi),
+            delta_xi=float(delta_xi),
+        )
+        return idx, count
+    idx, count, _ = _afa_select_torch(G, w, xi, delta_xi)
+    return idx, count
+
+
+def afa_select(
+    X: torch.Tensor, weights=None, xi: float = 2.0, delta_xi: float = 0.5
+) -> torch.Tensor:
+    """AFA's good set as a bool (n,) mask (see ``afa``)."""
+    if not _gpu(X):
+        return F.afa_select(X, weights, xi, delta_xi)
+    n = X.shape[0]
+    idx, count = afa_select_from_gram(gram(X), weights, xi, delta_xi)
+    live = (torch.arange(n, device=X.device) < count).to(torch.int32)
+    hits = torch.zeros(n, dtype=torch.int32, device=X.device)
+    return hits.scatter_add_(0, idx.long(), live) > 0
+
+
+def afa(
+    X: torch.Tensor, weights=None, xi: float = 2.0, delta_xi: float = 0.5
+) -> torch.Tensor:
+    """AFA: the weighted mean of the rows that survive the cosine-outlier
+    passes, zeros if none does (skip the round). ``weights`` (n,) >= 0,
+    default all ones. On device to AFA_MAX_N rows: MFMA Gram, one selection
+    launch, counted gather-mean (the un-weighted kernel when ``weights`` is
+    None) — three binding calls, no host sync, capturable into a hipGraph.
+    Past the cap the selection runs as torch ops on the device and syncs.
+    CPU tensors take the functional path."""
+    if not _gpu(X):
+        return F.afa(X, weights, xi, delta_xi)
+    idx, count = afa_select_from_gram(gram(X), weights, xi, delta_xi)
+    if weights is None:
+        return mean_rows_counted(X, idx, count)
+    w = _afa_device_weights(weights, X.shape[0], X.device)
+    return mean_rows_counted(X, idx, count, weights=w)
 
 
 def group_mean_rows(X: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:

@@ -246,6 +246,109 @@ def dnc(
     return X[good].float().mean(dim=0).to(X.dtype)
 
 
+# AFA, Adaptive Federated Averaging (Muñoz-González, Co, Lupu 2019,
+# Algorithm 1) without its cross-round state: the reputation that the paper
+# carries from round to round enters as ``weights`` (aggregators.AFAReputation
+# keeps it).
+
+
+def _afa_weights(weights, n: int) -> torch.Tensor:
+    """The (n,) f64 CPU weight vector after the argument checks."""
+    if weights is None:
+        return torch.ones(n, dtype=torch.float64)
+    w = torch.as_tensor(weights).detach().double().cpu().flatten()
+    if w.numel() != n:
+        raise ValueError(f"weights: expected {n} entries, got {w.numel()}")
+    if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+        raise ValueError("weights must be finite and >= 0")
+    return w
+
+
+def _afa_check(xi: float, delta_xi: float) -> None:
+    if not (xi >= 0 and math.isfinite(xi)):
+        raise ValueError(f"AFA needs a finite xi >= 0, got {xi}")
+    if not (delta_xi >= 0 and math.isfinite(delta_xi)):
+        raise ValueError(f"AFA needs a finite delta_xi >= 0, got {delta_xi}")
+
+
+def afa_trace(
+    X: torch.Tensor, weights=None, xi: float = 2.0, delta_xi: float = 0.5
+) -> Tuple[torch.Tensor, List[dict]]:
+    """AFA's selection with its working: (alive bool (n,), one record per
+    loop pass). A record holds ``alive`` (the set the pass started from),
+    ``s`` (f64 (n,) cosines, 0 outside alive), ``mean``, ``med``, ``sd``,
+    ``lower`` (the branch taken), ``threshold`` and ``removed`` (bool (n,)).
+    The last record of a run that ends by finding nothing to remove has an
+    all-false ``removed``. Everything is f64 on the CPU, from the explicit
+    weighted mean vector and explicit norms."""
+    _afa_check(xi, delta_xi)
+    n = X.shape[0]
+    w = _afa_weights(weights, n)
+    Xd = X.detach().float().double().cpu()
+    alive = torch.isfinite(Xd).all(dim=1) & (w > 0)
+    norms = torch.zeros(n, dtype=torch.float64)
+    norms[alive] = Xd[alive].pow(2).sum(dim=1).sqrt()
+    xi = float(xi)
+    trace: List[dict] = []
+    for _ in range(n):
+        if not bool(alive.any()):
+            break
+        rows = torch.nonzero(alive).flatten()
+        wa = w[rows]
+        g = (wa[:, None] * Xd[rows]).sum(dim=0) / wa.sum()
+        gn = float(g.pow(2).sum().sqrt())
+        s = torch.zeros(n, dtype=torch.float64)
+        for i in rows.tolist():
+            if gn > 0.0 and float(norms[i]) > 0.0:
+                s[i] = float((g * Xd[i]).sum()) / (gn * float(norms[i]))
+        sa = s[rows]
+        m = int(sa.numel())
+        mean = float(sa.sum()) / m
+        srt = torch.sort(sa).values
+        med = 0.5 * (float(srt[(m - 1) // 2]) + float(srt[m // 2]))
+        sd = math.sqrt(float(((sa - mean) ** 2).sum()) / m)
+        lower = mean < med
+        threshold = med - xi * sd if lower else med + xi * sd
+        removed = alive & ((s < threshold) if lower else (s > threshold))
+        trace.append(dict(
+            alive=alive.clone(), s=s, mean=mean, med=med, sd=sd, lower=lower,
+            threshold=threshold, removed=removed,
+        ))
+        if not bool(removed.any()):
+            break
+        alive = alive & ~removed
+        xi += float(delta_xi)
+    return alive, trace
+
+
+def afa_select(
+    X: torch.Tensor, weights=None, xi: float = 2.0, delta_xi: float = 0.5
+) -> torch.Tensor:
+    """AFA's good set, bool (n,). Start from the finite rows of positive
+    weight; each pass takes the weighted mean g of the rows still alive,
+    their cosines s_i to g (0 where a norm is 0), and the mean, true median
+    and population sd of s; if mean < median it drops the rows with
+    s_i < med - xi sd, else those with s_i > med + xi sd (strict, so sd = 0
+    drops nothing); xi grows by delta_xi after every pass that dropped a
+    row, and the first pass that drops none ends the loop. This is the
+    oracle."""
+    return afa_trace(X, weights, xi, delta_xi)[0]
+
+
+def afa(
+    X: torch.Tensor, weights=None, xi: float = 2.0, delta_xi: float = 0.5
+) -> torch.Tensor:
+    """AFA: the weighted mean of the rows of afa_select, the zero vector when
+    there is none (skip the round). Rows outside the good set are not read."""
+    good = afa_select(X, weights, xi, delta_xi)
+    if not bool(good.any()):
+        return torch.zeros_like(X[0])
+    w = _afa_weights(weights, X.shape[0])[good]
+    rows = X[good.to(X.device)].detach().float().double().cpu()
+    out = (w[:, None] * rows).sum(dim=0) / w.sum()
+    return out.to(dtype=X.dtype, device=X.device)
+
+
 def geometric_median(
     X: torch.Tensor,
     *,

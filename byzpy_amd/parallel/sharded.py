@@ -85,6 +85,21 @@ def dnc(
     return D.mean_rows_counted(X_local, idx, count)
 
 
+def afa(
+    X_local: torch.Tensor, weights=None, xi: float = 2.0, delta_xi: float = 0.5
+) -> torch.Tensor:
+    """AFA on a d-shard: one (n, n) all-reduce of the partial Gram, the
+    selection on it — identical on every rank, as the all-reduce returns the
+    same bits to all — and the counted (weighted) mean of the local shard."""
+    idx, count = D.afa_select_from_gram(
+        _global_gram(X_local), weights, xi, delta_xi
+    )
+    if weights is None:
+        return D.mean_rows_counted(X_local, idx, count)
+    w = D._afa_device_weights(weights, X_local.shape[0], X_local.device)
+    return D.mean_rows_counted(X_local, idx, count, weights=w)
+
+
 def krum(X_local: torch.Tensor, f: int) -> torch.Tensor:
     scores = D.krum_scores_from_gram(_global_gram(X_local), f)
     return X_local[int(torch.argmin(scores))].clone()
