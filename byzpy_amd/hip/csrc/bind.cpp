@@ -1,6 +1,7 @@
 // Python bindings for the byzpy_amd gfx950 kernel library.
 // Built in-tree by hip/build.py with explicit hipcc (no hipify, no CUDA
 // shims). Each op: validate, allocate, launch on the current stream.
+#include <cstdlib>
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 
@@ -140,8 +141,21 @@ torch::Tensor colsel_with_gram(const torch::Tensor& X, int64_t mode, int64_t f,
     check_colsel_f(mode, f, n);
     auto out = torch::empty({d}, X.options());
     G.zero_();
+    torch::Tensor ticket;
+    unsigned long long* ticket_ptr = nullptr;
+    // BYZPY_MEDIAN_GRAM_TICKET=1 / 0 forces the work counter on / off (the
+    // tests reach the ticketed loop at small d with it)
+    const char* force = std::getenv("BYZPY_MEDIAN_GRAM_TICKET");
+    const bool ticketed = (force != nullptr && (force[0] == '0' || force[0] == '1'))
+                              ? force[0] == '1'
+                              : median_gram_bf16_ticketed(d);
+    if (ticketed) {
+      ticket = torch::zeros({1}, X.options().dtype(torch::kInt64));
+      ticket_ptr =
+          reinterpret_cast<unsigned long long*>(ticket.data_ptr<int64_t>());
+    }
     launch_median_gram_bf16(ptr<__hip_bfloat16>(X), ptr<__hip_bfloat16>(out),
-                            f32(G), (int)n, d, cur_stream());
+                            f32(G), ticket_ptr, (int)n, d, cur_stream());
     return out;
   }
   auto out = colsel(X, mode, f, c10::nullopt, c10::nullopt);

@@ -405,9 +405,18 @@ DEV void bitonic_sort_pk(u32 (&v)[P]) {
 // The schedule is Batcher's odd-even merge sort (oem_sort.h): 191
 // compare-exchanges per 32 keys against the bitonic network's 240 at the
 // same depth — 196 packed ops fewer per column pair on a VALU-bound kernel.
-template <int P2, bool UP>
-DEV void oem_sort_pk_half(u32 (&v)[P2]) {
+//
+// `tick(k)` runs before every group of k packed ops here and in
+// pk_median_select; the default does nothing. median_gram_bf16_kernel uses
+// it to drop its Gram work between the ops at chosen op counts.
+struct NoTick {
+  DEV void operator()(int) const {}
+};
+
+template <int P2, bool UP, typename Tick = NoTick>
+DEV void oem_sort_pk_half(u32 (&v)[P2], Tick&& tick = Tick{}) {
   auto ce = [&](int lo, int hi) __attribute__((always_inline)) {
+    tick(2);
     const u32 a = v[lo], b = v[hi];
     v[lo] = pk_min_u16(a, b);
     v[hi] = pk_max_u16(a, b);
@@ -418,10 +427,12 @@ DEV void oem_sort_pk_half(u32 (&v)[P2]) {
 // packed twin of median_select_reg (see its comment): split the bitonic
 // [asc P/2 | desc P/2] keys, then max-reduce the lower / min-reduce the
 // upper half — both columns of the pair in one packed op throughout
-template <int P>
-DEV void pk_median_select(u32 (&v)[P], u32& mlo, u32& mhi) {
+template <int P, typename Tick = NoTick>
+DEV void pk_median_select(u32 (&v)[P], u32& mlo, u32& mhi,
+                          Tick&& tick = Tick{}) {
 #pragma unroll
   for (int i = 0; i < P / 2; ++i) {
+    tick(2);
     const u32 a = v[i], b = v[i + P / 2];
     v[i] = pk_min_u16(a, b);
     v[i + P / 2] = pk_max_u16(a, b);
@@ -430,6 +441,7 @@ DEV void pk_median_select(u32 (&v)[P], u32& mlo, u32& mhi) {
   for (int s = P / 4; s >= 1; s >>= 1)
 #pragma unroll
     for (int i = 0; i < s; ++i) {
+      tick(2);
       v[i] = pk_max_u16(v[i], v[i + s]);
       v[P / 2 + i] = pk_min_u16(v[P / 2 + i], v[P / 2 + s + i]);
     }
@@ -671,138 +683,302 @@ colsel_pk_median_bf16(const unsigned short* __restrict__ X,
 // The median side is colsel_pk_median_bf16<64> unchanged: every lane holds
 // its column pair in 64 registers and runs the selection network, so the
 // result bits are the separate kernel's. What is new is that each lane also
-// drops its raw loaded words into an LDS image of the tile, and between
-// tiles the SAME four waves run the Gram MFMAs from that image. The two
-// phases are time-sliced inside a wave, so the only Gram state that lives
-// through a sort is 16 accumulator registers, and X is read once.
+// drops its raw loaded words into an LDS image, and the SAME wave runs the
+// Gram MFMAs of its own columns from that image in the issue gaps of its
+// own sort. X is read once.
 //
-// Tile: 64 rows x 512 columns (256 lanes x one column pair). LDS image
-// [64][512] bf16 with a 16 B row pad (MG_ROW_BYTES = 1040, 66,560 B: two
-// blocks per CU):
-//  - store: lane t writes dword `row * 260 + t` — one base VGPR plus an
-//    immediate (63 * 1040 fits the 16-bit field); 32 consecutive lanes hit
-//    32 consecutive banks;
-//  - fragment read: in k-step s lane (r = l & 15, q = l >> 4) reads the
-//    16 B slot 16 * q + s of row r of a 16-row block. A Gram sums over k,
-//    so which 8 columns a (q, s) pair names is free as long as the A and B
-//    fragments agree, and over q < 4, s < 16 all 64 slots are covered.
-//    Bank row start = (4 * (65 * r + 16 * q + s)) mod 64 = 4 * ((r + s) mod
-//    16): distinct for the 16 rows whatever q they carry, so each of
-//    ds_read_b128's 16-lane groups — contiguous or not — is conflict-free.
+// A wave works on strips of 64 rows x 128 columns (64 lanes x one column
+// pair), and the strip's image is the wave's PRIVATE LDS slab: the wave
+// accumulates the whole 64 x 64 Gram of its slab (upper triangle: 10 tiles
+// of 16x16, 40 accumulator registers, v_mfma_f32_16x16x32_bf16 — the
+// 32x32x16 form would take 48 registers and 768 matrix-pipe cycles per
+// strip against 640), so no wave ever reads what another wave wrote and the
+// strip loop has NO block barrier: the LDS serves one wave's operations in
+// order, and a wave-scope fence keeps the compiler from moving the reads
+// over the stores.
 //
-// Wave w accumulates output rows [16w, 16w + 16) x all 64 columns as four
-// 16x16 tiles; tile j is column block (w + j) & 3, so fragment 0 is also
-// the A operand and a k-step costs 4 ds_read_b128 + 4 MFMAs with every
-// register index compile-time.
+// Slab: [64 rows][256 B + 16 B pad] (MG_ROW_BYTES = 272, 17,408 B per wave,
+// 69,632 B per block: two blocks per CU):
+//  - store: lane l writes dword l of row i — one base VGPR plus an
+//    immediate; 32 consecutive lanes hit 32 consecutive banks;
+//  - fragment read: four k-steps of 32 per strip. ds_read_b128 is served in
+//    four NON-contiguous 16-lane groups; with r = l & 15, q = l >> 4 a group
+//    carries rows {0-3, 12-15} of one q and rows {4-11} of its neighbour
+//    q ^ 1. A row holds only 16 slots of 16 B, so the two q of a group must
+//    read different slots c, and with a 17-slot row stride the group's bank
+//    quads are (row + c) mod 16. Rows 8-11 and 12-15 of every 16-row block
+//    therefore swap places in the image (mg_phys_row): a group then holds
+//    image rows {0-3, 8-11} of one q and {4-7, 12-15} of the other, and
+//    slots that differ by 8 make the two sets tile all 16 bank quads. Lane
+//    (r, q) reads slot 8 * (q & 1) + 4 * (q >> 1) + s in k-step s: over
+//    q < 4, s < 4 all 16 slots once. A Gram sums over k, so which 8 columns
+//    a (q, s) names is free as long as the A and B fragments agree — and
+//    they are the same registers.
 //
-// The next tile's 64 raw words are loaded into a second register set right
-// after the current tile's words have been stored and turned into keys, so
-// they stay in flight through the whole sort and the MFMA phase: at two
-// waves per SIMD that prefetch, not occupancy, hides the HBM latency.
+// A k-step is 4 ds_read_b128 (one fragment per 16-row block) + 10 MFMAs
+// (blocks a <= b), spread through the selection network: each MFMA is
+// followed by a run of the network's v_pk_min/max, so the matrix work sits
+// in the VALU stream's issue gaps instead of a phase of its own. The places
+// are fixed in the source (a hook in the network counts its ops, full
+// scheduling barriers pin each event); a sched_group_barrier pipeline over
+// the 890-op network was not honoured by the compiler.
+//
+// The next strip's 64 raw words are loaded into a second register set right
+// after the current strip's words have been stored and turned into keys, so
+// they stay in flight through the whole sort: at two waves per SIMD that
+// prefetch, not occupancy, hides the HBM latency. The row walk is a
+// wave-uniform base (strip start, advanced by the row stride on the scalar
+// unit) plus one 32-bit per-lane byte offset below 1 KiB, so the loads are
+// global_load_dword v, v, s[..] with no vector address arithmetic and no
+// limit on the row length.
 //
 // Rows >= n and lanes past d / 2 put zeros in the image (their loads are
-// clamped to valid addresses and nothing is stored for them). Each block
-// owns a contiguous run of tiles and ends with one atomicAdd of its partial
-// Gram into the caller-zeroed G.
+// clamped to valid addresses and nothing is stored for them).
+//
+// At large d strips are handed out, not split evenly: with an even static
+// split the average wave was done after 75-85 % of the kernel's time and
+// the slowest set it. Each wave starts on its own chunk of consecutive
+// strips and draws every further chunk from a caller-zeroed ticket counter,
+// one chunk ahead. Below median_gram_bf16_ticketed(d) there is no ticket
+// and every wave takes one even share (profiles/r04_median_gram_wave.md has
+// the sizes measured either way).
+//
+// At the end the four waves of a block park their partials in the (now
+// free) slabs, one barrier, and every thread sums the four partials of 10
+// entries and adds each into the caller-zeroed G at (i, j) and, off the
+// diagonal blocks, (j, i): 4,096 atomics per block.
 // ---------------------------------------------------------------------------
 
 typedef __attribute__((ext_vector_type(8))) __bf16 mg_bf16x8;
 typedef __attribute__((ext_vector_type(4))) float mg_f32x4;
 
 constexpr int MG_THREADS = 256;
-constexpr int MG_PAIRS = MG_THREADS;               // column pairs per tile
-constexpr int MG_ROW_BYTES = MG_PAIRS * 4 + 16;    // 1040
-constexpr int MG_ROW_WORDS = MG_ROW_BYTES / 4;     // 260
-constexpr int MG_LDS_BYTES = 64 * MG_ROW_BYTES;    // 66,560
+constexpr int MG_ROW_BYTES = 64 * 4 + 16;          // 272: one wave's row + pad
+constexpr int MG_SLAB_BYTES = 64 * MG_ROW_BYTES;   // 17,408
+constexpr int MG_LDS_BYTES = 4 * MG_SLAB_BYTES;    // 69,632
+constexpr int MG_TILES = 10;                       // 16x16 blocks a <= b
+constexpr int MG_CHUNK = 8;                        // strips per ticket draw
 
-// pinned load walk of one tile's 64 row words (see colsel_reg_kernel's load
-// phase); `p` is the lane's clamped pair in row 0
-template <int P>
-DEV void mg_load_tile(u32 (&r)[P], const u32* p, long rowstride, int n) {
-  if (n == P) {
+// image row of matrix row i: rows 8-11 and 12-15 of each 16-row block swap
+constexpr int mg_phys_row(int i) {
+  const int r = i & 15;
+  return (i & ~15) | (r < 8 ? r : (r < 12 ? r + 4 : r - 4));
+}
+
+// index of block (a, b), a <= b, in the 10-tile upper triangle
+constexpr int mg_tile(int a, int b) { return 4 * a - a * (a - 1) / 2 + (b - a); }
+
+// pinned load walk of one strip's 64 row words (see colsel_reg_kernel's load
+// phase): `base` is the strip's first pair in row 0 (wave-uniform), `off` the
+// lane's clamped byte offset inside the strip, `rowbytes` the row stride
+template <int P, bool FULL>
+DEV void mg_load_tile(u32 (&r)[P], const char* base, u32 off, long rowbytes,
+                      int n) {
+  if (FULL) {
 #pragma unroll
     for (int i = 0; i < P; ++i) {
-      r[i] = *p;
-      if (i + 1 < P) p += rowstride;
+      r[i] = *reinterpret_cast<const u32*>(base + off);
+      if (i + 1 < P) base += rowbytes;
       __builtin_amdgcn_sched_barrier(0);
     }
   } else {
+    // the walk stops at row n - 1; slots past it repeat that row and the
+    // pad logic overwrites them. Per-lane pointer with a predicated step:
+    // on the scalar unit the 63 chosen steps are loop-invariant, get
+    // hoisted out of the strip loop into 126 SGPRs and spill
+    const char* p = base + off;
     const int n_walk = vecify(n);
 #pragma unroll
     for (int i = 0; i < P; ++i) {
-      r[i] = *p;
-      p += (i + 1 < n_walk) ? rowstride : 0;
+      r[i] = *reinterpret_cast<const u32*>(p);
+      p += (i + 1 < n_walk) ? rowbytes : 0;
       __builtin_amdgcn_sched_barrier(0);
     }
   }
 }
 
+// Where the Gram work of a strip sits in the selection network's packed ops
+// (two half-sorts of 191 compare-exchanges, the 32 compare-exchanges of the
+// split and its 2 x 31 reductions): k-step s starts at op MG_STEP * s with
+// its 4 fragment reads, MG_LEAD ops cover their latency, then its 10 MFMAs
+// follow MG_GAP ops apart. Events the network did not reach are issued
+// right after it (see the kernel), so a shorter network costs speed, never
+// a missing MFMA.
+constexpr int MG_NET_OPS = 2 * (2 * 191) + 2 * 32 + 2 * 31;  // 890
+constexpr int MG_STEP = 222, MG_LEAD = 32, MG_GAP = 19;
+constexpr int MG_EVENTS = 4 * (1 + MG_TILES);
+static_assert(3 * MG_STEP + MG_LEAD + (MG_TILES - 1) * MG_GAP <= MG_NET_OPS - 2,
+              "the last MFMA must be due before the network's last group");
+
+// Orders this wave's LDS accesses before the fence against those after it,
+// for the compiler only: the LDS serves one wave's operations in order.
+DEV void mg_wave_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// FULL: n == 64 (no pad slots, no row clamp), chosen by the launcher so
+// that each instantiation has ONE load walk: with both in one kernel the
+// prefetched words reach the loop's end through 33 register copies.
+template <bool FULL>
 __global__ void __launch_bounds__(MG_THREADS, 2)
 median_gram_bf16_kernel(const unsigned short* __restrict__ X,
                         unsigned short* __restrict__ out,
-                        float* __restrict__ G, int n, long d,
-                        long tiles_per_block) {
+                        float* __restrict__ G, int n, long d, int chunk,
+                        unsigned long long* __restrict__ ticket) {
   constexpr int P = 64;
   __shared__ __attribute__((aligned(16))) char img[MG_LDS_BYTES];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const long npairs = d >> 1;
-  const long rowstride = npairs;  // in u32 units
-  const long ntiles = (npairs + MG_PAIRS - 1) / MG_PAIRS;
-  const long t_lo = (long)blockIdx.x * tiles_per_block;
-  const long t_hi = min(ntiles, t_lo + tiles_per_block);
-  if (t_lo >= t_hi) return;  // the whole block leaves before any barrier
+  // A wave's unit of work is a strip: 64 rows x 128 columns, the column
+  // pairs [64 u, 64 u + 64). Strips go out in chunks of `chunk` consecutive
+  // ones: wave g of the grid starts on chunk g, every later chunk comes off
+  // the caller-zeroed ticket counter, drawn one chunk ahead so that the
+  // atomic's round trip hides behind a chunk of work.
+  const long nstrips = (npairs + 63) / 64;
+  const long nwaves = (long)gridDim.x * (MG_THREADS / 64);
+  auto draw = [&]() {
+    if (ticket == nullptr) return 0x3fffffffffffffffL;  // even split: no more
+    unsigned long long got = 0;
+    if (lane == 0)
+      got = __hip_atomic_fetch_add(ticket, (unsigned long long)chunk,
+                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const u32 lo = __builtin_amdgcn_readfirstlane((u32)got);
+    const u32 hi = __builtin_amdgcn_readfirstlane((u32)(got >> 32));
+    return nwaves * chunk + (long)(((unsigned long long)hi << 32) | lo);
+  };
+  long u = ((long)blockIdx.x * (MG_THREADS / 64) + wave) * chunk;
+  long chunk_end = u + chunk;
+  long next_chunk = draw();
 
-  const u32* Xw = reinterpret_cast<const u32*>(X);
+  const char* Xb = reinterpret_cast<const char*>(X);
   u32* outw = reinterpret_cast<u32*>(out);
-  u32* const wr = reinterpret_cast<u32*>(img) + tid;
-  const char* rd[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    rd[j] = img + (16 * ((wave + j) & 3) + (lane & 15)) * MG_ROW_BYTES +
-            (lane >> 4) * 256;
+  const long rowbytes = npairs * 4;
+  char* const slab = img + wave * MG_SLAB_BYTES;
+  char* const wr = slab + 4 * lane;
+  const int fr = lane & 15, fq = lane >> 4;
+  const char* const rd = slab + mg_phys_row(fr) * MG_ROW_BYTES +
+                         16 * (8 * (fq & 1) + 4 * (fq >> 1));
 
-  mg_f32x4 acc[4];
+  mg_f32x4 acc[MG_TILES];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) acc[j] = mg_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  for (int e = 0; e < MG_TILES; ++e) acc[e] = mg_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 
   const int nv = vecify(n);
   // MEDIAN pad split, as in colsel_pk_median_bf16
   const int n_lo = vecify(n + (P / 2 - 1 - ((n - 1) >> 1)));
 
-  u32 r[P];
-  mg_load_tile<P>(r, Xw + min(t_lo * MG_PAIRS + tid, npairs - 1), rowstride, n);
+  // loads of strip s, per lane clamped to the row's last pair. A strip past
+  // the end is never used: the wave reads `own` (in range) again instead,
+  // its own strip and not the matrix's last one, where every wave of a
+  // small call would meet.
+  auto load_strip = [&](u32 (&dst)[P], long s, long own)
+      __attribute__((always_inline)) {
+    s = s < nstrips ? s : own;
+    const u32 off = (u32)min((long)lane, npairs - 1 - s * 64) * 4u;
+    mg_load_tile<P, FULL>(dst, Xb + s * 256, off, rowbytes, n);
+  };
 
-  for (long t = t_lo; t < t_hi; ++t) {
-    const long pair = t * MG_PAIRS + tid;
+  u32 r[P];
+  load_strip(r, u, nstrips - 1);
+
+  while (u < nstrips) {
+    const long pair = u * 64 + lane;
     const bool valid = pair < npairs;
     u32 v[P];
-    // raw words into the image, then keys; r is dead after this
-    if (n == P && (t + 1) * MG_PAIRS <= npairs) {
+    mg_wave_fence();  // the last strip's fragment reads stay above the stores
+    // raw words into the slab, then keys; r is dead after this
+    if (FULL && (u + 1) * 64 <= npairs) {
 #pragma unroll
-      for (int i = 0; i < P; ++i) wr[i * MG_ROW_WORDS] = r[i];
+      for (int i = 0; i < P; ++i)
+        *reinterpret_cast<u32*>(wr + mg_phys_row(i) * MG_ROW_BYTES) = r[i];
     } else {
       const int n_img = valid ? nv : 0;
 #pragma unroll
       for (int i = 0; i < P; ++i)
-        wr[i * MG_ROW_WORDS] = (i < n_img) ? r[i] : 0u;
+        *reinterpret_cast<u32*>(wr + mg_phys_row(i) * MG_ROW_BYTES) =
+            (i < n_img) ? r[i] : 0u;
     }
 #pragma unroll
     for (int i = 0; i < P; ++i) v[i] = pk_key_from_bf16(r[i]);
-    if (n < P) {
+    if (!FULL) {
+      // slots [n, n_lo) pad low, [n_lo, P) pad high (n > P / 2 here). The
+      // bounds go through opaque per-tile copies: hoisted out of the tile
+      // loop, the 31 pad words and their masks would stay live through it
+      // and spill
+      int nv_t = nv, n_lo_t = n_lo;
+      asm volatile("" : "+v"(nv_t), "+v"(n_lo_t));
 #pragma unroll
-      for (int i = 0; i < P; ++i)
-        if (i >= nv) v[i] = (i < n_lo) ? 0u : 0xFFFFFFFFu;
+      for (int i = P / 2 + 1; i < P; ++i) {
+        if (i >= nv_t) v[i] = 0u;
+        if (i >= n_lo_t) v[i] = 0xFFFFFFFFu;
+      }
     }
-    if (t + 1 < t_hi)
-      mg_load_tile<P>(r, Xw + min(pair + MG_PAIRS, npairs - 1), rowstride, n);
+    // the next strip: the chunk's next one, or the first of the chunk drawn
+    // a chunk ago (and then the draw for the one after)
+    long u_next = u + 1;
+    if (u_next == chunk_end) {
+      u_next = next_chunk;
+      chunk_end = next_chunk + chunk;
+      next_chunk = draw();
+    }
+    // unconditional: behind a branch the 64 words come back through copies
+    // at the loop's end
+    load_strip(r, u_next, u);
+    mg_wave_fence();  // the slab is complete for this wave's own reads
 
-    oem_sort_pk_half<P / 2, true>(*reinterpret_cast<u32(*)[P / 2]>(&v[0]));
+    // Gram of the slab inside the selection network. Event 11 * s + m is
+    // k-step s's fragment reads (m == 0: one per 16-row block) or its MFMA
+    // m - 1 (blocks a <= b); an event runs once the network has issued the
+    // op count it is due at, and a full scheduling barrier on either side
+    // pins that place (with one side open an MFMA floats up to its reads).
+    // `ops` and `ev` are compile-time once the network unrolls.
+    mg_bf16x8 f[4];
+    int ops = 0, ev = 0;
+    auto tick = [&](int k) __attribute__((always_inline)) {
+      const int s = ev / (1 + MG_TILES), m = ev % (1 + MG_TILES);
+      const int due =
+          MG_STEP * s + (m == 0 ? 0 : MG_LEAD + MG_GAP * (m - 1));
+      if (ev < MG_EVENTS && ops >= due) {
+        __builtin_amdgcn_sched_barrier(0);
+        if (m == 0) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            f[j] = *reinterpret_cast<const mg_bf16x8*>(
+                rd + 16 * j * MG_ROW_BYTES + 16 * s);
+        } else {
+#pragma unroll
+          for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = a; b < 4; ++b)
+              if (mg_tile(a, b) == m - 1)
+                acc[mg_tile(a, b)] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                    f[a], f[b], acc[mg_tile(a, b)], 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        ++ev;
+      }
+      ops += k;
+    };
+    oem_sort_pk_half<P / 2, true>(*reinterpret_cast<u32(*)[P / 2]>(&v[0]),
+                                  tick);
     oem_sort_pk_half<P / 2, false>(
-        *reinterpret_cast<u32(*)[P / 2]>(&v[P / 2]));
+        *reinterpret_cast<u32(*)[P / 2]>(&v[P / 2]), tick);
     u32 lo, hi;
-    pk_median_select<P>(v, lo, hi);
+    pk_median_select<P>(v, lo, hi, tick);
+    // whatever the network did not reach (nothing, with the constants above)
+#pragma unroll
+    for (int k = 0; k < MG_EVENTS; ++k) {
+      ops = MG_NET_OPS * 4;
+      tick(0);
+    }
+    // pins the network in this block: left alone it sinks, whole, into the
+    // `valid` branch of the store below, away from the MFMAs
+    asm volatile("" : "+v"(lo), "+v"(hi));
+
     if (n & 1) hi = lo;
     const float m0 =
         0.5f * (key_to_float(lo & 0xFFFFu) + key_to_float(hi & 0xFFFFu));
@@ -814,45 +990,51 @@ median_gram_bf16_kernel(const unsigned short* __restrict__ X,
     o.s[0] = c0.s;
     o.s[1] = c1.s;
     if (valid) outw[pair] = o.w;
+    u = u_next;
+  }
 
-    __syncthreads();  // the image is complete
-    // k-step s + 1's four fragment reads issue ahead of k-step s's MFMAs
-    // (left alone the scheduler waits out every read in front of its MFMA);
-    // the group barriers pin that 4-read / 4-MFMA alternation
-    mg_bf16x8 f[2][4];
+  // Block epilogue. Wave w parks register q of tile e at float
+  // (4 * e + q) * 64 + lane of its own slab (its reads are done: the MFMAs
+  // consumed them); after the barrier thread (w, lane) owns register w of
+  // every tile. C/D map for 16x16: col = lane & 15, row = (lane >> 4) * 4 +
+  // register.
+  mg_wave_fence();
+  float* const part = reinterpret_cast<float*>(slab) + lane;
 #pragma unroll
-    for (int j = 0; j < 4; ++j)
-      f[0][j] = *reinterpret_cast<const mg_bf16x8*>(rd[j]);
-    __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+  for (int e = 0; e < MG_TILES; ++e)
 #pragma unroll
-    for (int s = 0; s < 16; ++s) {
-      if (s + 1 < 16) {
+    for (int q = 0; q < 4; ++q) part[(4 * e + q) * 64] = acc[e][q];
+  __syncthreads();
+  const float* const sum =
+      reinterpret_cast<const float*>(img) + wave * 64 + lane;
+  const float* const mirror = reinterpret_cast<const float*>(img) +
+                              (fr & 3) * 64 + 16 * (fr >> 2) + 4 * fq + wave;
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
-          f[(s + 1) & 1][j] =
-              *reinterpret_cast<const mg_bf16x8*>(rd[j] + (s + 1) * 16);
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = a; b < 4; ++b) {
+      float g = 0.0f;
+#pragma unroll
+      for (int w = 0; w < 4; ++w)
+        g += sum[w * (MG_SLAB_BYTES / 4) + 4 * mg_tile(a, b) * 64];
+      const int row = 16 * a + (lane >> 4) * 4 + wave;
+      const int col = 16 * b + (lane & 15);
+      if (row < n && col < n) atomicAdd(&G[(long)row * n + col], g);
+      if (a != b) {
+        // the mirror image, with the lanes along G's rows again: this
+        // thread takes tile element (fr, 4 * fq + wave), which sits in
+        // register fr & 3 of lane 16 * (fr >> 2) + 4 * fq + wave. Written
+        // from `g` above the 16 lanes of a row group would hit 16 cache
+        // lines, and the atomics are what a small call spends its time on.
+        float gt = 0.0f;
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+          gt += mirror[w * (MG_SLAB_BYTES / 4) + 4 * mg_tile(a, b) * 64];
+        const int mrow = 16 * b + 4 * fq + wave;
+        const int mcol = 16 * a + fr;
+        if (mrow < n && mcol < n) atomicAdd(&G[(long)mrow * n + mcol], gt);
       }
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            f[s & 1][0], f[s & 1][j], acc[j], 0, 0, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);  // 4 LDS reads
-      __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);  // 4 MFMAs
     }
-    __syncthreads();  // every wave has read it: the next tile may overwrite
-  }
-
-  // C/D map for 16x16: col = lane & 15, row = (lane >> 4) * 4 + reg
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int out_col = 16 * ((wave + j) & 3) + (lane & 15);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int out_row = 16 * wave + (lane >> 4) * 4 + q;
-      if (out_row < n && out_col < n)
-        atomicAdd(&G[(long)out_row * n + out_col], acc[j][q]);
-    }
-  }
 }
 
 // (the specialized 2-pass 256-bin bf16 median radix kernels that lived
@@ -1080,23 +1262,31 @@ void launch_colsel<__hip_bfloat16>(const __hip_bfloat16* X,
   colsel_generic(X, out, n, d, mode, f, rows, n_src, stream);
 }
 
-// Persistent grid: two blocks per CU (what the 66,560 B image admits), each
-// with a contiguous run of tiles.
+// Persistent grid: two blocks per CU (what the 69,632 B of slabs admit);
+// the waves draw their strips in chunks from `ticket`.
 void launch_median_gram_bf16(const __hip_bfloat16* X, __hip_bfloat16* med,
-                             float* G, int n, long d, hipStream_t stream) {
+                             float* G, unsigned long long* ticket, int n,
+                             long d, hipStream_t stream) {
   int dev = 0, cus = 0;
   if (hipGetDevice(&dev) != hipSuccess ||
       hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
                             dev) != hipSuccess ||
       cus < 1)
     cus = 256;
-  const long ntiles = ((d >> 1) + MG_PAIRS - 1) / MG_PAIRS;
+  const long nstrips = ((d >> 1) + 63) / 64;
   const long want = 2L * cus;
-  const long blocks = ntiles < want ? ntiles : want;
-  const long tiles_per_block = (ntiles + blocks - 1) / blocks;
-  hipLaunchKernelGGL(median_gram_bf16_kernel, dim3((unsigned)blocks),
-                     dim3(MG_THREADS), 0, stream,
+  const long need = (nstrips + 3) / 4;
+  const long blocks = need < want ? need : want;
+  // With a ticket: chunks of MG_CHUNK strips (the draws all hit one address
+  // and cost ~20 ns each in a row, so they must stay far apart). Without:
+  // an even split, one chunk per wave.
+  const long nwaves = 4 * blocks;
+  const int chunk =
+      ticket != nullptr ? MG_CHUNK : (int)((nstrips + nwaves - 1) / nwaves);
+  hipLaunchKernelGGL(n == 64 ? median_gram_bf16_kernel<true>
+                             : median_gram_bf16_kernel<false>,
+                     dim3((unsigned)blocks), dim3(MG_THREADS), 0, stream,
                      reinterpret_cast<const unsigned short*>(X),
-                     reinterpret_cast<unsigned short*>(med), G, n, d,
-                     tiles_per_block);
+                     reinterpret_cast<unsigned short*>(med), G, n, d, chunk,
+                     ticket);
 }

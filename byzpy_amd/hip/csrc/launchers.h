@@ -39,8 +39,13 @@ void launch_colsel(const T* X, T* out, int n, long d, int mode, int f,
 inline bool median_gram_bf16_applies(long n, long d) {
   return n > 32 && n <= 64 && d >= 2 && (d % 2) == 0;
 }
+// `ticket` is one caller-zeroed 64-bit device word (the kernel's work
+// counter) where median_gram_bf16_ticketed(d), else null: from 2^18 strips
+// of 128 columns up the waves draw their work instead of splitting it evenly.
+inline bool median_gram_bf16_ticketed(long d) { return d >= (1L << 25); }
 void launch_median_gram_bf16(const __hip_bfloat16* X, __hip_bfloat16* med,
-                             float* G, int n, long d, hipStream_t stream);
+                             float* G, unsigned long long* ticket, int n,
+                             long d, hipStream_t stream);
 
 // rsel.hip: streaming radix-select engine for large n, same modes.
 // `state` is caller-zeroed d*4 u32 scratch; `med` is a d-float scratch,

@@ -128,10 +128,14 @@ def median_and_gram(X: torch.Tensor):
     32 < n <= 64 rows and an even d >= MEDIAN_GRAM_FUSED_MIN_D take ONE
     pass over X (``colsel(X, 0, 0, gram=G)``): every lane keeps its column
     pair in registers and runs the median's selection network exactly as
-    the separate kernel does, drops the raw words into an LDS image on the
-    way, and the same waves run the Gram MFMAs from that image between
-    tiles (profiles/r03_median_gram_fused.md; the six organizations that
-    lost are in profiles/r02_fusion_negative.md). The median is bitwise
+    the separate kernel does and drops the raw words into its wave's private
+    LDS slab (64 rows x 128 columns) on the way; the wave accumulates the
+    upper triangle of that slab's Gram with MFMAs placed inside its own
+    selection network, so the loop has no block barrier, and waves draw
+    their 128-column strips from a work counter
+    (profiles/r04_median_gram_wave.md, r03_median_gram_fused.md; the six
+    organizations that lost are in profiles/r02_fusion_negative.md). The
+    median is bitwise
     the separate kernel's; the Gram differs from ``gram(X)`` only in f32
     summation order. Everything else, and ``BYZPY_MEDIAN_GRAM=split``,
     runs ``median(X), gram(X)``."""
