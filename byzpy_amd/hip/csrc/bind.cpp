@@ -125,7 +125,9 @@ torch::Tensor colsel(torch::Tensor X, int64_t mode, int64_t f,
 // colsel(X, 0, f, gram=G): the column median, and G overwritten with
 // X X^T. One pass over X where the fused kernel applies (bf16,
 // 32 < n <= 64, even d), else the median and Gram launches one after the
-// other, so the call means the same for every input.
+// other, so the call means the same for every input. The fused launcher
+// checks G's diagonal on the device and reruns the median kernel if an
+// entry is not finite, so G has to be zeroed and filled by THIS call.
 torch::Tensor colsel_with_gram(const torch::Tensor& X, int64_t mode, int64_t f,
                                bool has_rows, const torch::Tensor& G) {
   TORCH_CHECK(mode == 0, "colsel(gram=) computes the median: expected mode 0, ",

@@ -335,9 +335,11 @@ colsel_reg_kernel(const T* __restrict__ X, T* __restrict__ out,
 // Packed bf16 median (n <= 64, even d): TWO adjacent columns per thread.
 // Order statistics only need a monotone key, so bf16 values become
 // sortable u16 keys (sign-flip transform) and the sorting networks run on
-// v_pk_min_u16 / v_pk_max_u16 — one instruction per compare-exchange for
-// BOTH columns (no packed f32 min/max exists on gfx950), with half the
-// register footprint (P u32 regs for 2 columns) and 4 B/lane loads.
+// v_pk_min_u16 / v_pk_max_u16 — one instruction per HALF of a
+// compare-exchange (a compare-exchange is the min and the max of the same
+// two registers: two packed ops) for BOTH columns (no packed f32 min/max
+// exists on gfx950), with half the register footprint (P u32 regs for 2
+// columns) and 4 B/lane loads.
 // ---------------------------------------------------------------------------
 
 DEV u32 pk_min_u16(u32 a, u32 b) {
@@ -350,6 +352,37 @@ DEV u32 pk_max_u16(u32 a, u32 b) {
   asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
   return r;
 }
+
+// The packed pair a selection network runs on (oem_sort_pk_half,
+// pk_median_select). PkKeyU16 orders sortable u16 keys (pk_key_from_bf16).
+// PkRawF16 orders RAW bf16 words with no transform at all: a bf16 word is
+// sign | monotone magnitude and so is an f16 word, so read as f16 two bf16
+// patterns compare exactly as the values they encode — as long as neither
+// is an f16 NaN or infinity, i.e. magnitude bits < 0x7C00, |x| < 2^121
+// (63,488 of the 65,536 patterns). The pair returns its two inputs bit for
+// bit (f16 subnormals pass through: the kernels keep f16 denormals on) and
+// orders -0 below +0 in either operand order, as the u16 keys do
+// (benchmarks/csrc/pkminprobe.hip measures both, and that the f16 pair
+// issues as fast as the u16 pair). Callers must rule the other 2,048
+// patterns out themselves (median_gram_bf16_kernel: its Gram's diagonal).
+struct PkKeyU16 {
+  static DEV u32 mn(u32 a, u32 b) { return pk_min_u16(a, b); }
+  static DEV u32 mx(u32 a, u32 b) { return pk_max_u16(a, b); }
+};
+struct PkRawF16 {
+  static DEV u32 mn(u32 a, u32 b) {
+    u32 r;
+    asm("v_pk_min_f16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+  }
+  static DEV u32 mx(u32 a, u32 b) {
+    u32 r;
+    asm("v_pk_max_f16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+  }
+};
+// pad words of PkRawF16 for slots past n: the extreme legal patterns
+constexpr u32 PK_RAW_PAD_LO = 0xFBFFFBFFu, PK_RAW_PAD_HI = 0x7BFF7BFFu;
 
 // bf16 bits -> sortable u16 key, two lanes at once: per half
 // key = bits ^ (sign ? 0xFFFF : 0x8000). The packed arithmetic shift
@@ -413,13 +446,13 @@ struct NoTick {
   DEV void operator()(int) const {}
 };
 
-template <int P2, bool UP, typename Tick = NoTick>
+template <int P2, bool UP, typename OP = PkKeyU16, typename Tick = NoTick>
 DEV void oem_sort_pk_half(u32 (&v)[P2], Tick&& tick = Tick{}) {
   auto ce = [&](int lo, int hi) __attribute__((always_inline)) {
     tick(2);
     const u32 a = v[lo], b = v[hi];
-    v[lo] = pk_min_u16(a, b);
-    v[hi] = pk_max_u16(a, b);
+    v[lo] = OP::mn(a, b);
+    v[hi] = OP::mx(a, b);
   };
   oem::sort<P2, UP>(ce);
 }
@@ -427,23 +460,23 @@ DEV void oem_sort_pk_half(u32 (&v)[P2], Tick&& tick = Tick{}) {
 // packed twin of median_select_reg (see its comment): split the bitonic
 // [asc P/2 | desc P/2] keys, then max-reduce the lower / min-reduce the
 // upper half — both columns of the pair in one packed op throughout
-template <int P, typename Tick = NoTick>
+template <int P, typename OP = PkKeyU16, typename Tick = NoTick>
 DEV void pk_median_select(u32 (&v)[P], u32& mlo, u32& mhi,
                           Tick&& tick = Tick{}) {
 #pragma unroll
   for (int i = 0; i < P / 2; ++i) {
     tick(2);
     const u32 a = v[i], b = v[i + P / 2];
-    v[i] = pk_min_u16(a, b);
-    v[i + P / 2] = pk_max_u16(a, b);
+    v[i] = OP::mn(a, b);
+    v[i + P / 2] = OP::mx(a, b);
   }
 #pragma unroll
   for (int s = P / 4; s >= 1; s >>= 1)
 #pragma unroll
     for (int i = 0; i < s; ++i) {
       tick(2);
-      v[i] = pk_max_u16(v[i], v[i + s]);
-      v[P / 2 + i] = pk_min_u16(v[P / 2 + i], v[P / 2 + s + i]);
+      v[i] = OP::mx(v[i], v[i + s]);
+      v[P / 2 + i] = OP::mn(v[P / 2 + i], v[P / 2 + s + i]);
     }
   mlo = v[0];
   mhi = v[P / 2];
@@ -463,7 +496,14 @@ DEV u32 extract_at_pk(const u32 (&v)[P], int pos) {
 // independent sorting networks; QUADS=false: one pair (4 B/lane).
 // MODE: MEDIAN or TRIMMED (order statistics read straight off the sorted
 // keys; TRIMMED unpacks the kept range and sums in f32).
-template <int P, bool QUADS, int MODE, bool ROWS>
+//
+// GUARD = true is the fallback of the fused median + Gram call
+// (launch_median_gram_bf16): `guard_G` is the (n, n) Gram, and every wave
+// returns at once, `out` untouched, if all n diagonal entries are finite
+// (one 4 B/lane read, n <= 64 lanes); else the kernel runs as always. It is
+// an instantiation of its own, so that GUARD = false, which never looks at
+// `guard_G`, keeps the instruction stream it had without it.
+template <int P, bool QUADS, int MODE, bool ROWS, bool GUARD = false>
 __global__ void
 // QUADS at P=64 holds two 64-u32 arrays (~150 VGPRs): ask for 3 waves/SIMD
 // so the allocator doesn't cap at 128 and spill
@@ -474,7 +514,15 @@ colsel_pk_median_bf16(const unsigned short* __restrict__ X,
                                       unsigned short* __restrict__ out, int n,
                                       long d, int f,
                                       const int* __restrict__ rows,
-                                      int n_src) {
+                                      int n_src,
+                                      const float* __restrict__ guard_G) {
+  if (GUARD) {
+    const int gl = threadIdx.x & 63;
+    // |g| < inf is false for +-inf and for NaN
+    const bool finite =
+        gl >= n || __builtin_fabsf(guard_G[(long)gl * n + gl]) < PAD;
+    if (__all(finite)) return;
+  }
   const long npairs = d >> 1;
   const long nunits = QUADS ? (npairs >> 1) : npairs;
   const long unit0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -680,12 +728,20 @@ colsel_pk_median_bf16(const unsigned short* __restrict__ X,
 // ---------------------------------------------------------------------------
 // Median + Gram in ONE pass over X (bf16, 32 < n <= 64, even d).
 //
-// The median side is colsel_pk_median_bf16<64> unchanged: every lane holds
-// its column pair in 64 registers and runs the selection network, so the
-// result bits are the separate kernel's. What is new is that each lane also
-// drops its raw loaded words into an LDS image, and the SAME wave runs the
-// Gram MFMAs of its own columns from that image in the issue gaps of its
-// own sort. X is read once.
+// The median side is colsel_pk_median_bf16<64>'s selection network on the
+// RAW loaded words: every lane holds its column pair in 64 registers and
+// runs the network with the packed f16 pair (PkRawF16) in place of the key
+// transform and the u16 pair, which orders every bf16 pattern below 2^121
+// in magnitude exactly as the keys do, so the result bits are the separate
+// kernel's. A word of 2^121 or more, an infinity or a NaN makes its row's
+// diagonal Gram entry non-finite (x^2 >= 2^242 overflows f32; diagonal
+// products are never negative, so nothing cancels), and the launcher's
+// second kernel (colsel_pk_median_bf16 with GUARD) then recomputes the
+// whole median with the u16-key kernel: a finite diagonal proves that every
+// word was legal. What is new against the separate kernel is that each lane
+// also drops its raw loaded words into an LDS image, and the SAME wave runs
+// the Gram MFMAs of its own columns from that image in the issue gaps of
+// its own sort. X is read once.
 //
 // A wave works on strips of 64 rows x 128 columns (64 lanes x one column
 // pair), and the strip's image is the wave's PRIVATE LDS slab: the wave
@@ -724,9 +780,12 @@ colsel_pk_median_bf16(const unsigned short* __restrict__ X,
 // the 890-op network was not honoured by the compiler.
 //
 // The next strip's 64 raw words are loaded into a second register set right
-// after the current strip's words have been stored and turned into keys, so
-// they stay in flight through the whole sort: at two waves per SIMD that
-// prefetch, not occupancy, hides the HBM latency. The row walk is a
+// after the current strip's words have been stored, so they stay in flight
+// through the whole sort: at two waves per SIMD that prefetch, not
+// occupancy, hides the HBM latency. The network sorts the loaded registers
+// in place, so the two sets swap roles from strip to strip: the strip loop
+// is unrolled by two with the sets exchanged, and no word is ever copied
+// from one set to the other. The row walk is a
 // wave-uniform base (strip start, advanced by the row stride on the scalar
 // unit) plus one 32-bit per-lane byte offset below 1 KiB, so the loads are
 // global_load_dword v, v, s[..] with no vector address arithmetic and no
@@ -882,28 +941,30 @@ median_gram_bf16_kernel(const unsigned short* __restrict__ X,
     mg_load_tile<P, FULL>(dst, Xb + s * 256, off, rowbytes, n);
   };
 
-  u32 r[P];
-  load_strip(r, u, nstrips - 1);
-
-  while (u < nstrips) {
+  // One strip: `v` holds strip u's 64 raw words on entry and is sorted in
+  // place; `r` receives the next strip's words.
+  auto strip = [&](u32 (&v)[P], u32 (&r)[P]) __attribute__((always_inline)) {
     const long pair = u * 64 + lane;
     const bool valid = pair < npairs;
-    u32 v[P];
     mg_wave_fence();  // the last strip's fragment reads stay above the stores
-    // raw words into the slab, then keys; r is dead after this
+    // raw words into the slab
     if (FULL && (u + 1) * 64 <= npairs) {
 #pragma unroll
       for (int i = 0; i < P; ++i)
-        *reinterpret_cast<u32*>(wr + mg_phys_row(i) * MG_ROW_BYTES) = r[i];
+        *reinterpret_cast<u32*>(wr + mg_phys_row(i) * MG_ROW_BYTES) = v[i];
+    } else if (FULL) {
+      // the matrix's last strip: every row is real, tail lanes are not
+#pragma unroll
+      for (int i = 0; i < P; ++i)
+        *reinterpret_cast<u32*>(wr + mg_phys_row(i) * MG_ROW_BYTES) =
+            valid ? v[i] : 0u;
     } else {
       const int n_img = valid ? nv : 0;
 #pragma unroll
       for (int i = 0; i < P; ++i)
         *reinterpret_cast<u32*>(wr + mg_phys_row(i) * MG_ROW_BYTES) =
-            (i < n_img) ? r[i] : 0u;
+            (i < n_img) ? v[i] : 0u;
     }
-#pragma unroll
-    for (int i = 0; i < P; ++i) v[i] = pk_key_from_bf16(r[i]);
     if (!FULL) {
       // slots [n, n_lo) pad low, [n_lo, P) pad high (n > P / 2 here). The
       // bounds go through opaque per-tile copies: hoisted out of the tile
@@ -913,8 +974,8 @@ median_gram_bf16_kernel(const unsigned short* __restrict__ X,
       asm volatile("" : "+v"(nv_t), "+v"(n_lo_t));
 #pragma unroll
       for (int i = P / 2 + 1; i < P; ++i) {
-        if (i >= nv_t) v[i] = 0u;
-        if (i >= n_lo_t) v[i] = 0xFFFFFFFFu;
+        if (i >= nv_t) v[i] = PK_RAW_PAD_LO;
+        if (i >= n_lo_t) v[i] = PK_RAW_PAD_HI;
       }
     }
     // the next strip: the chunk's next one, or the first of the chunk drawn
@@ -963,12 +1024,12 @@ median_gram_bf16_kernel(const unsigned short* __restrict__ X,
       }
       ops += k;
     };
-    oem_sort_pk_half<P / 2, true>(*reinterpret_cast<u32(*)[P / 2]>(&v[0]),
-                                  tick);
-    oem_sort_pk_half<P / 2, false>(
+    oem_sort_pk_half<P / 2, true, PkRawF16>(
+        *reinterpret_cast<u32(*)[P / 2]>(&v[0]), tick);
+    oem_sort_pk_half<P / 2, false, PkRawF16>(
         *reinterpret_cast<u32(*)[P / 2]>(&v[P / 2]), tick);
     u32 lo, hi;
-    pk_median_select<P>(v, lo, hi, tick);
+    pk_median_select<P, PkRawF16>(v, lo, hi, tick);
     // whatever the network did not reach (nothing, with the constants above)
 #pragma unroll
     for (int k = 0; k < MG_EVENTS; ++k) {
@@ -979,10 +1040,12 @@ median_gram_bf16_kernel(const unsigned short* __restrict__ X,
     // `valid` branch of the store below, away from the MFMAs
     asm volatile("" : "+v"(lo), "+v"(hi));
 
+    // lo and hi are bf16 bits: a bf16 is the upper half of its f32
     if (n & 1) hi = lo;
     const float m0 =
-        0.5f * (key_to_float(lo & 0xFFFFu) + key_to_float(hi & 0xFFFFu));
-    const float m1 = 0.5f * (key_to_float(lo >> 16) + key_to_float(hi >> 16));
+        0.5f * (__uint_as_float(lo << 16) + __uint_as_float(hi << 16));
+    const float m1 = 0.5f * (__uint_as_float(lo & 0xFFFF0000u) +
+                             __uint_as_float(hi & 0xFFFF0000u));
     union { unsigned short s[2]; u32 w; } o;
     union { unsigned short s; __hip_bfloat16 h; } c0, c1;
     c0.h = __float2bfloat16(m0);
@@ -991,6 +1054,16 @@ median_gram_bf16_kernel(const unsigned short* __restrict__ X,
     o.s[1] = c1.s;
     if (valid) outw[pair] = o.w;
     u = u_next;
+  };
+
+  // two register sets that swap roles: the set a strip was prefetched into
+  // is the set it is sorted in
+  u32 ra[P], rb[P];
+  load_strip(ra, u, nstrips - 1);
+  while (u < nstrips) {
+    strip(ra, rb);
+    if (!(u < nstrips)) break;
+    strip(rb, ra);
   }
 
   // Block epilogue. Wave w parks register q of tile e at float
@@ -998,17 +1071,24 @@ median_gram_bf16_kernel(const unsigned short* __restrict__ X,
   // consumed them); after the barrier thread (w, lane) owns register w of
   // every tile. C/D map for 16x16: col = lane & 15, row = (lane >> 4) * 4 +
   // register.
+  // The lane's coordinates are worked out again, from the lane counter and
+  // not from the thread index: kept from the kernel's start they (or the
+  // thread index) would hold, through the whole strip loop, registers that
+  // the two word sets need (they spilled).
+  const int ln =
+      __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+  const int er = ln & 15, eq = ln >> 4;
   mg_wave_fence();
-  float* const part = reinterpret_cast<float*>(slab) + lane;
+  float* const part = reinterpret_cast<float*>(slab) + ln;
 #pragma unroll
   for (int e = 0; e < MG_TILES; ++e)
 #pragma unroll
     for (int q = 0; q < 4; ++q) part[(4 * e + q) * 64] = acc[e][q];
   __syncthreads();
   const float* const sum =
-      reinterpret_cast<const float*>(img) + wave * 64 + lane;
+      reinterpret_cast<const float*>(img) + wave * 64 + ln;
   const float* const mirror = reinterpret_cast<const float*>(img) +
-                              (fr & 3) * 64 + 16 * (fr >> 2) + 4 * fq + wave;
+                              (er & 3) * 64 + 16 * (er >> 2) + 4 * eq + wave;
 #pragma unroll
   for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -1017,21 +1097,21 @@ median_gram_bf16_kernel(const unsigned short* __restrict__ X,
 #pragma unroll
       for (int w = 0; w < 4; ++w)
         g += sum[w * (MG_SLAB_BYTES / 4) + 4 * mg_tile(a, b) * 64];
-      const int row = 16 * a + (lane >> 4) * 4 + wave;
-      const int col = 16 * b + (lane & 15);
+      const int row = 16 * a + (ln >> 4) * 4 + wave;
+      const int col = 16 * b + (ln & 15);
       if (row < n && col < n) atomicAdd(&G[(long)row * n + col], g);
       if (a != b) {
         // the mirror image, with the lanes along G's rows again: this
-        // thread takes tile element (fr, 4 * fq + wave), which sits in
-        // register fr & 3 of lane 16 * (fr >> 2) + 4 * fq + wave. Written
+        // thread takes tile element (er, 4 * eq + wave), which sits in
+        // register er & 3 of lane 16 * (er >> 2) + 4 * eq + wave. Written
         // from `g` above the 16 lanes of a row group would hit 16 cache
         // lines, and the atomics are what a small call spends its time on.
         float gt = 0.0f;
 #pragma unroll
         for (int w = 0; w < 4; ++w)
           gt += mirror[w * (MG_SLAB_BYTES / 4) + 4 * mg_tile(a, b) * 64];
-        const int mrow = 16 * b + 4 * fq + wave;
-        const int mcol = 16 * a + fr;
+        const int mrow = 16 * b + 4 * eq + wave;
+        const int mcol = 16 * a + er;
         if (mrow < n && mcol < n) atomicAdd(&G[(long)mrow * n + mcol], gt);
       }
     }
@@ -1239,7 +1319,7 @@ void launch_colsel<__hip_bfloat16>(const __hip_bfloat16* X,
       const int qgrid = capped_grid(d >> 2, block);
       hipLaunchKernelGGL((colsel_pk_median_bf16<64, true, MEDIAN, false>),
                          dim3(qgrid), dim3(block), 0, stream, Xu, Ou, n, d, f,
-                         rows, n_src);
+                         rows, n_src, (const float*)nullptr);
       return;
     }
     by_mode(mode, [&](auto m) {
@@ -1253,7 +1333,7 @@ void launch_colsel<__hip_bfloat16>(const __hip_bfloat16* X,
           hipLaunchKernelGGL(
               (colsel_pk_median_bf16<decltype(p)::value, false, MODE, ROWS>),
               dim3(grid), dim3(block), lds, stream, Xu, Ou, n, d, f, rows,
-              n_src);
+              n_src, (const float*)nullptr);
         });
       });
     });
@@ -1289,4 +1369,17 @@ void launch_median_gram_bf16(const __hip_bfloat16* X, __hip_bfloat16* med,
                      reinterpret_cast<const unsigned short*>(X),
                      reinterpret_cast<unsigned short*>(med), G, n, d, chunk,
                      ticket);
+  // The fused kernel's network is only right for words below 2^121 in
+  // magnitude; G's diagonal tells (see the kernel's header). Next on the
+  // stream, no host sync: the u16-key median over all of X into `med`,
+  // which every wave leaves at once when the diagonal is finite. The grid
+  // is capped at four blocks per CU and strides, so that the launch that
+  // has nothing to do costs a few microseconds.
+  const long gwant = (long)capped_grid(d >> 1, 256);
+  const long gcap = 4L * cus;
+  hipLaunchKernelGGL((colsel_pk_median_bf16<64, false, MEDIAN, false, true>),
+                     dim3((unsigned)(gwant < gcap ? gwant : gcap)), dim3(256),
+                     0, stream, reinterpret_cast<const unsigned short*>(X),
+                     reinterpret_cast<unsigned short*>(med), n, d, 0,
+                     (const int*)nullptr, 0, (const float*)G);
 }

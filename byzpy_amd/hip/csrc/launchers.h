@@ -35,7 +35,12 @@ void launch_colsel(const T* X, T* out, int n, long d, int mode, int f,
 // colsel.hip: column median and Gram X X^T in one pass over X. bf16 only;
 // `med` receives what launch_colsel(mode 0) writes, bit for bit, and the
 // partial Grams are ADDED into the caller-zeroed (n, n) G. Call it only
-// where median_gram_bf16_applies(n, d).
+// where median_gram_bf16_applies(n, d). Two launches on `stream`: the fused
+// kernel, whose median is right when every |x| < 2^121, and a guard that
+// reads G's diagonal on the device and, if any entry is not finite, runs
+// launch_colsel's median kernel over X into `med` (else it returns at
+// once). G must therefore be this call's own Gram, not yet reduced with
+// anyone else's.
 inline bool median_gram_bf16_applies(long n, long d) {
   return n > 32 && n <= 64 && d >= 2 && (d % 2) == 0;
 }

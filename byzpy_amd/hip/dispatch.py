@@ -127,8 +127,10 @@ def median_and_gram(X: torch.Tensor):
     """Both flagship aggregates: (median, gram). bf16 device matrices with
     32 < n <= 64 rows and an even d >= MEDIAN_GRAM_FUSED_MIN_D take ONE
     pass over X (``colsel(X, 0, 0, gram=G)``): every lane keeps its column
-    pair in registers and runs the median's selection network exactly as
-    the separate kernel does and drops the raw words into its wave's private
+    pair in registers and runs the separate kernel's selection network on
+    the RAW bf16 words with the packed f16 min/max pair (no key transform:
+    read as f16, bf16 patterns below 2^121 in magnitude order as their
+    values do) and drops the raw words into its wave's private
     LDS slab (64 rows x 128 columns) on the way; the wave accumulates the
     upper triangle of that slab's Gram with MFMAs placed inside its own
     selection network, so the loop has no block barrier, and waves draw
@@ -136,9 +138,14 @@ def median_and_gram(X: torch.Tensor):
     (profiles/r04_median_gram_wave.md, r03_median_gram_fused.md; the six
     organizations that lost are in profiles/r02_fusion_negative.md). The
     median is bitwise
-    the separate kernel's; the Gram differs from ``gram(X)`` only in f32
-    summation order. Everything else, and ``BYZPY_MEDIAN_GRAM=split``,
-    runs ``median(X), gram(X)``."""
+    the separate kernel's for EVERY input: a word of 2^121 or more, an
+    infinity or a NaN leaves a non-finite entry on G's diagonal, which a
+    second launch on the same stream checks on the device (no host sync;
+    a few microseconds when there is nothing to do) before it recomputes
+    the median with the separate kernel
+    (profiles/r05_median_gram_rawbits.md). The Gram differs from
+    ``gram(X)`` only in f32 summation order. Everything else, and
+    ``BYZPY_MEDIAN_GRAM=split``, runs ``median(X), gram(X)``."""
     if _median_gram_fused_ok(X):
         Xc = X.contiguous()
         G = torch.empty((X.shape[0], X.shape[0]), dtype=torch.float32,
