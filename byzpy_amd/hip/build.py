@@ -21,7 +21,7 @@ BUILD_DIR = PKG_DIR.parent / "build" / "hip"
 
 SOURCES = ["colsel.hip", "rsel.hip", "rowops.hip", "gram.hip", "krumsel.hip",
            "subsets.hip", "attacks.hip", "mda_host.cpp", "bind.cpp"]
-HEADERS = ["common.h", "launchers.h", "mda_host.h", "oem_sort.h"]
+HEADERS = ["common.h", "launchers.h", "mda_host.h", "oem_sort.h", "selnet.h"]
 
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 

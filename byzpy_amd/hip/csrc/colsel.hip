@@ -10,7 +10,10 @@
 //    sorting network is fully unrolled so every index is compile-time
 //    (guide §5.4 rule 20 — runtime-indexed register arrays spill).
 //    Order statistics at runtime positions are extracted with predicated
-//    unrolled scans for the same reason.
+//    unrolled scans for the same reason. The networks themselves (bitonic
+//    sort, half sort, median selection, pad split) are the templates of
+//    selnet.h, written once for f32 registers and packed words; this file
+//    supplies their min/max policies, the loads, the pads and the epilogues.
 //  - LDS kernel (64 < n <= 512): one wave per block, each lane owns a
 //    column staged in LDS with a +1 pad row stride (bank-conflict free,
 //    guide §6 G4); runtime bitonic loops.
@@ -21,8 +24,7 @@
 // row-iteration is one 256 B (f32) / 128 B (bf16) wave transaction.
 #include "common.h"
 #include "launchers.h"
-#include "oem_sort.h"
-#include <cstdlib>
+#include "selnet.h"
 #include <type_traits>
 
 namespace {
@@ -110,32 +112,14 @@ DEV bool wave_active(long unit, long nunits) {
 // register variant, n <= P, P in {8, 16, 32, 64}
 // ---------------------------------------------------------------------------
 
-// KMAX < P stops the network after phase KMAX: with KMAX = P/2 the two
-// halves come out sorted ascending/descending — exactly the input the
-// median SELECTION epilogue needs (see median_select_reg), at the cost
-// of the full sort minus its entire last merge phase (log2(P) substages).
-template <int P, int KMAX = P>
-DEV void bitonic_sort_reg(float (&v)[P]) {
-#pragma unroll
-  for (int k = 2; k <= KMAX; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j > 0; j >>= 1) {
-#pragma unroll
-      for (int i = 0; i < P; ++i) {
-        const int l = i ^ j;
-        if (l > i) {
-          const bool asc = (i & k) == 0;
-          const float a = v[i], b = v[l];
-          const float lo = fminf(a, b), hi = fmaxf(a, b);
-          v[i] = asc ? lo : hi;
-          v[l] = asc ? hi : lo;
-        }
-      }
-    }
-  }
-}
+// min/max policy of the selnet.h networks on f32 registers
+struct F32MinMax {
+  static DEV float mn(float a, float b) { return fminf(a, b); }
+  static DEV float mx(float a, float b) { return fmaxf(a, b); }
+};
 
-// key-value variant (sort k ascending, carry v along)
+// key-value bitonic sort (sort key ascending, carry val along): it swaps on
+// a comparison, so it is not a min/max network and stays here
 template <int P>
 DEV void bitonic_sort_kv_reg(float (&key)[P], float (&val)[P]) {
 #pragma unroll
@@ -158,53 +142,6 @@ DEV void bitonic_sort_kv_reg(float (&key)[P], float (&val)[P]) {
   }
 }
 
-// Median ranks P/2-1 and P/2 of [asc32 | desc32] (a bitonic sequence):
-// one elementwise min/max pass splits it into the smallest and largest
-// P/2 multisets, then rank P/2-1 = max(lower), rank P/2 = min(upper) —
-// 3P/2 - 2 ops replacing the last merge phase (P/2*log2(P) CEs) PLUS the
-// two O(P) predicated rank extractions. The caller pre-pads so the
-// median lands exactly on these ranks (see the MEDIAN pad split below).
-template <int P>
-DEV void median_select_reg(float (&v)[P], float& mlo, float& mhi) {
-#pragma unroll
-  for (int i = 0; i < P / 2; ++i) {
-    const float a = v[i], b = v[i + P / 2];
-    v[i] = fminf(a, b);
-    v[i + P / 2] = fmaxf(a, b);
-  }
-#pragma unroll
-  for (int s = P / 4; s >= 1; s >>= 1)
-#pragma unroll
-    for (int i = 0; i < s; ++i) {
-      v[i] = fmaxf(v[i], v[i + s]);
-      v[P / 2 + i] = fminf(v[P / 2 + i], v[P / 2 + s + i]);
-    }
-  mlo = v[0];
-  mhi = v[P / 2];
-}
-
-// standalone half-sort (see oem_sort_pk_half for why source order matters
-// and for the network): UP=true ascending, UP=false the mirrored descending
-// network
-template <int P2, bool UP>
-DEV void oem_sort_reg_half(float (&v)[P2]) {
-  auto ce = [&](int lo, int hi) __attribute__((always_inline)) {
-    const float a = v[lo], b = v[hi];
-    v[lo] = fminf(a, b);
-    v[hi] = fmaxf(a, b);
-  };
-  oem::sort<P2, UP>(ce);
-}
-
-template <int P>
-DEV float extract_at(const float (&v)[P], int pos) {
-  float r = 0.0f;
-#pragma unroll
-  for (int i = 0; i < P; ++i)
-    if (i == pos) r = v[i];
-  return r;
-}
-
 // Indexed load phase shared by the register kernels: element I of `dst`
 // comes from at_row<I>(base). Same pinned load/advance alternation as
 // the plain walk (see the load-phase comment in colsel_reg_kernel).
@@ -224,9 +161,9 @@ DEV void load_rows_indexed(E (&dst)[P], const E* base, const RowOffsets& ro) {
 // keep the default 4-waves/SIMD occupancy.
 template <int P, int MODE, typename T, bool ROWS>
 __global__ void
-__launch_bounds__(256, (MODE == 2 && P >= 64)           ? 2
-                       : (ROWS && MODE == 1 && P >= 64) ? 3
-                                                        : 4)
+__launch_bounds__(256, (MODE == MEAMED && P >= 64)            ? 2
+                       : (ROWS && MODE == TRIMMED && P >= 64) ? 3
+                                                              : 4)
 colsel_reg_kernel(const T* __restrict__ X, T* __restrict__ out,
                                   int n, long d, int f,
                                   const int* __restrict__ rows, int n_src) {
@@ -262,12 +199,12 @@ colsel_reg_kernel(const T* __restrict__ X, T* __restrict__ out,
 
     float result;
     if (MODE == MEDIAN) {
-      // selection network, half at a time IN SOURCE ORDER (see the pk
-      // kernel): half A's conversion+sort consume only the first P/2
-      // loads and overlap the tail loads. MEDIAN pads split: L low pads
-      // (-inf) shift the median ranks to exactly P/2-1 / P/2; a -inf
-      // pad tying a -inf data value is value-identical.
-      const int n_lo = vecify(n + (P / 2 - 1 - ((n - 1) >> 1)));
+      // selection network; each half is converted and padded right
+      // before its sort (selnet::half_sort has why), so half A's work
+      // overlaps the tail loads. Pad split: the low pads (-inf) put the
+      // median on ranks P/2-1 / P/2; a -inf pad tying a -inf data value
+      // is value-identical.
+      const int n_lo = vecify(selnet::median_pad_split<P>(n));
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const int base = h * (P / 2);
@@ -279,14 +216,12 @@ colsel_reg_kernel(const T* __restrict__ X, T* __restrict__ out,
             if (i >= nv) v[i] = (i < n_lo) ? -PAD : PAD;
         }
         if (h == 0)
-          oem_sort_reg_half<P / 2, true>(
-              *reinterpret_cast<float(*)[P / 2]>(&v[0]));
+          selnet::half_sort<P / 2, true, F32MinMax>(selnet::half<0>(v));
         else
-          oem_sort_reg_half<P / 2, false>(
-              *reinterpret_cast<float(*)[P / 2]>(&v[P / 2]));
+          selnet::half_sort<P / 2, false, F32MinMax>(selnet::half<1>(v));
       }
       float mlo, mhi;
-      median_select_reg<P>(v, mlo, mhi);
+      selnet::median_select<P, F32MinMax>(v, mlo, mhi);
       result = (n & 1) ? mlo : 0.5f * (mlo + mhi);
     } else if (MODE == TRIMMED) {
 #pragma unroll
@@ -296,7 +231,7 @@ colsel_reg_kernel(const T* __restrict__ X, T* __restrict__ out,
         for (int i = 0; i < P; ++i)
           if (i >= nv) v[i] = PAD;
       }
-      bitonic_sort_reg<P>(v);
+      selnet::bitonic_sort<P, F32MinMax>(v);
       const int fv = vecify(f), nfv = vecify(n - f);
       float s = 0.0f;
 #pragma unroll
@@ -311,10 +246,10 @@ colsel_reg_kernel(const T* __restrict__ X, T* __restrict__ out,
         for (int i = 0; i < P; ++i)
           if (i >= nv) v[i] = PAD;
       }
-      bitonic_sort_reg<P>(v);
+      selnet::bitonic_sort<P, F32MinMax>(v);
       const int pos_lo = vecify((n - 1) >> 1), pos_hi = vecify(n >> 1);
       const float med =
-          0.5f * (extract_at<P>(v, pos_lo) + extract_at<P>(v, pos_hi));
+          0.5f * (selnet::extract_at(v, pos_lo) + selnet::extract_at(v, pos_hi));
       const int nv2 = vecify(n), nfv = vecify(n - f);
       float dev[P];
 #pragma unroll
@@ -342,20 +277,8 @@ colsel_reg_kernel(const T* __restrict__ X, T* __restrict__ out,
 // columns) and 4 B/lane loads.
 // ---------------------------------------------------------------------------
 
-DEV u32 pk_min_u16(u32 a, u32 b) {
-  u32 r;
-  asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-DEV u32 pk_max_u16(u32 a, u32 b) {
-  u32 r;
-  asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-
-// The packed pair a selection network runs on (oem_sort_pk_half,
-// pk_median_select). PkKeyU16 orders sortable u16 keys (pk_key_from_bf16).
-// PkRawF16 orders RAW bf16 words with no transform at all: a bf16 word is
+// The min/max policies of the selnet.h networks on packed words. PkKeyU16
+// orders sortable u16 keys (pk_key_from_bf16). PkRawF16 orders RAW bf16 words with no transform at all: a bf16 word is
 // sign | monotone magnitude and so is an f16 word, so read as f16 two bf16
 // patterns compare exactly as the values they encode — as long as neither
 // is an f16 NaN or infinity, i.e. magnitude bits < 0x7C00, |x| < 2^121
@@ -366,8 +289,16 @@ DEV u32 pk_max_u16(u32 a, u32 b) {
 // issues as fast as the u16 pair). Callers must rule the other 2,048
 // patterns out themselves (median_gram_bf16_kernel: its Gram's diagonal).
 struct PkKeyU16 {
-  static DEV u32 mn(u32 a, u32 b) { return pk_min_u16(a, b); }
-  static DEV u32 mx(u32 a, u32 b) { return pk_max_u16(a, b); }
+  static DEV u32 mn(u32 a, u32 b) {
+    u32 r;
+    asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+  }
+  static DEV u32 mx(u32 a, u32 b) {
+    u32 r;
+    asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+  }
 };
 struct PkRawF16 {
   static DEV u32 mn(u32 a, u32 b) {
@@ -408,94 +339,12 @@ DEV float key_to_float(u32 key16) {
   return __bfloat162float(c.h);
 }
 
-template <int P, int KMAX = P>
-DEV void bitonic_sort_pk(u32 (&v)[P]) {
-#pragma unroll
-  for (int k = 2; k <= KMAX; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j > 0; j >>= 1) {
-#pragma unroll
-      for (int i = 0; i < P; ++i) {
-        const int l = i ^ j;
-        if (l > i) {
-          const bool asc = (i & k) == 0;
-          const u32 a = v[i], b = v[l];
-          const u32 lo = pk_min_u16(a, b), hi = pk_max_u16(a, b);
-          v[i] = asc ? lo : hi;
-          v[l] = asc ? hi : lo;
-        }
-      }
-    }
-  }
-}
-
-// standalone half-sort for the median selection path: UP=true ascending,
-// UP=false the mirrored (descending) network. Sorting a half touches only
-// its own P2 registers, so in source order the FIRST half's compare-
-// exchanges issue while the second half's row loads are still in flight
-// (the shared <P, P/2> network's k=2 phase touches all P loads up front and
-// forces a full vmcnt(0) wait before any compute).
-// The schedule is Batcher's odd-even merge sort (oem_sort.h): 191
-// compare-exchanges per 32 keys against the bitonic network's 240 at the
-// same depth — 196 packed ops fewer per column pair on a VALU-bound kernel.
-//
-// `tick(k)` runs before every group of k packed ops here and in
-// pk_median_select; the default does nothing. median_gram_bf16_kernel uses
-// it to drop its Gram work between the ops at chosen op counts.
-struct NoTick {
-  DEV void operator()(int) const {}
-};
-
-template <int P2, bool UP, typename OP = PkKeyU16, typename Tick = NoTick>
-DEV void oem_sort_pk_half(u32 (&v)[P2], Tick&& tick = Tick{}) {
-  auto ce = [&](int lo, int hi) __attribute__((always_inline)) {
-    tick(2);
-    const u32 a = v[lo], b = v[hi];
-    v[lo] = OP::mn(a, b);
-    v[hi] = OP::mx(a, b);
-  };
-  oem::sort<P2, UP>(ce);
-}
-
-// packed twin of median_select_reg (see its comment): split the bitonic
-// [asc P/2 | desc P/2] keys, then max-reduce the lower / min-reduce the
-// upper half — both columns of the pair in one packed op throughout
-template <int P, typename OP = PkKeyU16, typename Tick = NoTick>
-DEV void pk_median_select(u32 (&v)[P], u32& mlo, u32& mhi,
-                          Tick&& tick = Tick{}) {
-#pragma unroll
-  for (int i = 0; i < P / 2; ++i) {
-    tick(2);
-    const u32 a = v[i], b = v[i + P / 2];
-    v[i] = OP::mn(a, b);
-    v[i + P / 2] = OP::mx(a, b);
-  }
-#pragma unroll
-  for (int s = P / 4; s >= 1; s >>= 1)
-#pragma unroll
-    for (int i = 0; i < s; ++i) {
-      tick(2);
-      v[i] = OP::mx(v[i], v[i + s]);
-      v[P / 2 + i] = OP::mn(v[P / 2 + i], v[P / 2 + s + i]);
-    }
-  mlo = v[0];
-  mhi = v[P / 2];
-}
-
-template <int P>
-DEV u32 extract_at_pk(const u32 (&v)[P], int pos) {
-  u32 r = 0;
-#pragma unroll
-  for (int i = 0; i < P; ++i)
-    if (i == pos) r = v[i];
-  return r;
-}
-
-// QUADS=true: each thread owns TWO adjacent packed pairs (4 columns,
-// 8 B/lane row reads — wider DRAM bursts; ~150 VGPRs at P=64) with two
-// independent sorting networks; QUADS=false: one pair (4 B/lane).
-// MODE: MEDIAN or TRIMMED (order statistics read straight off the sorted
-// keys; TRIMMED unpacks the kept range and sums in f32).
+// MODE: MEDIAN reads its order statistics off the selection network,
+// TRIMMED and MEAMED off the sorted keys (unpacked and summed in f32).
+// (A four-columns-per-lane variant of this kernel, 8 B/lane row reads and
+// two key arrays, was retired: its ~150 VGPRs allow 3 waves per SIMD against
+// this kernel's 5 and it measured 3x slower, 9.09 vs 3.09 ms at 64 x 125M;
+// docs/NOTES_R03.md, profiles/r01_bench125_kernel_stats.md.)
 //
 // GUARD = true is the fallback of the fused median + Gram call
 // (launch_median_gram_bf16): `guard_G` is the (n, n) Gram, and every wave
@@ -503,13 +352,9 @@ DEV u32 extract_at_pk(const u32 (&v)[P], int pos) {
 // (one 4 B/lane read, n <= 64 lanes); else the kernel runs as always. It is
 // an instantiation of its own, so that GUARD = false, which never looks at
 // `guard_G`, keeps the instruction stream it had without it.
-template <int P, bool QUADS, int MODE, bool ROWS, bool GUARD = false>
+template <int P, int MODE, bool ROWS, bool GUARD = false>
 __global__ void
-// QUADS at P=64 holds two 64-u32 arrays (~150 VGPRs): ask for 3 waves/SIMD
-// so the allocator doesn't cap at 128 and spill
-__launch_bounds__(256, (QUADS && P >= 64) ? 3
-                       : (MODE == MEDIAN && P >= 64) ? 5
-                                                     : 4)
+__launch_bounds__(256, (MODE == MEDIAN && P >= 64) ? 5 : 4)
 colsel_pk_median_bf16(const unsigned short* __restrict__ X,
                                       unsigned short* __restrict__ out, int n,
                                       long d, int f,
@@ -524,39 +369,29 @@ colsel_pk_median_bf16(const unsigned short* __restrict__ X,
     if (__all(finite)) return;
   }
   const long npairs = d >> 1;
-  const long nunits = QUADS ? (npairs >> 1) : npairs;
   const long unit0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long stride = (long)gridDim.x * blockDim.x;
   const long rowstride = d >> 1;  // in u32 units
   RowOffsets ro = {0u, 0u};
   if (ROWS) ro = stage_row_offsets(rows, n, n_src, rowstride * (long)sizeof(u32));
-  for (long unit = unit0; wave_active<ROWS>(unit, nunits); unit += stride) {
-    // ROWS: tail lanes of the last wave load a clamped (valid) unit and
+  for (long unit = unit0; wave_active<ROWS>(unit, npairs); unit += stride) {
+    // ROWS: tail lanes of the last wave load a clamped (valid) pair and
     // skip the store
-    const long ldunit = ROWS ? min(unit, nunits - 1) : unit;
-    const long pair = QUADS ? ldunit * 2 : ldunit;
-    u32 v[P], v2[QUADS ? P : 1];
+    const long pair = ROWS ? min(unit, npairs - 1) : unit;
+    u32 v[P];
     // raw loads first + pinned alternation: see colsel_reg_kernel's load
     // phase for why (one live base, no SGPR spill storm). The walk
     // condition is vecified too — 64 uniform selects otherwise become
-    // batched SGPR mask pairs and spill at QUADS register pressure.
+    // batched SGPR mask pairs.
     const u32* p = reinterpret_cast<const u32*>(X) + pair;
     if (ROWS) {
-      // indexed walk (pairs only: QUADS is an un-indexed A/B aid)
-      static_assert(!(ROWS && QUADS), "no indexed QUADS variant");
       load_rows_indexed<P>(v, p, ro);
     } else if (n == P) {
       // full tile (the flagship n=64 shape): unconditional walk, no pads
       // — drops ~190 predication VALU ops from a VALU-bound kernel
 #pragma unroll
       for (int i = 0; i < P; ++i) {
-        if (QUADS) {
-          const uint2 w = *reinterpret_cast<const uint2*>(p);
-          v[i] = w.x;
-          v2[i] = w.y;
-        } else {
-          v[i] = *p;
-        }
+        v[i] = *p;
         if (i + 1 < P) p += rowstride;
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -564,91 +399,60 @@ colsel_pk_median_bf16(const unsigned short* __restrict__ X,
       const int n_walk = vecify(n);
 #pragma unroll
       for (int i = 0; i < P; ++i) {
-        if (QUADS) {
-          const uint2 w = *reinterpret_cast<const uint2*>(p);
-          v[i] = w.x;
-          v2[i] = w.y;
-        } else {
-          v[i] = *p;
-        }
+        v[i] = *p;
         p += (i + 1 < n_walk) ? rowstride : 0;
         __builtin_amdgcn_sched_barrier(0);
       }
     }
     const int nv = vecify(n);  // conversion/pad loops + MEAMED epilogue
-    u32 sel_lo[2] = {0u, 0u}, sel_hi[2] = {0u, 0u};
+    u32 sel_lo = 0u, sel_hi = 0u;
     if (MODE == MEDIAN) {
-      // selection network, half at a time IN SOURCE ORDER: converting and
-      // sorting [0,P/2) consumes only the first P/2 row loads, so those
-      // 191 CEs overlap the in-flight tail loads; then the (mirrored
-      // descending) upper half, one split pass and two reductions.
-      // MEDIAN pads split low/high so the fixed ranks P/2-1 / P/2 hit
-      // the true median (low-pad key 0 only ties a negative-NaN data
-      // key — NaN order statistics are unspecified in the full-sort
-      // path too).
-      const int n_lo = vecify(n + (P / 2 - 1 - ((n - 1) >> 1)));
+      // selection network as in colsel_reg_kernel: key transform and pads
+      // per half, right before its sort. The low-pad key 0 only ties a
+      // negative-NaN data key (NaN order statistics are unspecified in the
+      // full-sort path too).
+      const int n_lo = vecify(selnet::median_pad_split<P>(n));
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const int base = h * (P / 2);
 #pragma unroll
-        for (int i = base; i < base + P / 2; ++i) {
+        for (int i = base; i < base + P / 2; ++i)
           v[i] = pk_key_from_bf16(v[i]);
-          if (QUADS) v2[i] = pk_key_from_bf16(v2[i]);
-        }
         if (n < P) {
 #pragma unroll
           for (int i = base; i < base + P / 2; ++i)
-            if (i >= nv) {
-              const u32 pad = (i < n_lo) ? 0u : 0xFFFFFFFFu;
-              v[i] = pad;
-              if (QUADS) v2[i] = pad;
-            }
+            if (i >= nv) v[i] = (i < n_lo) ? 0u : 0xFFFFFFFFu;
         }
-        if (h == 0) {
-          oem_sort_pk_half<P / 2, true>(
-              *reinterpret_cast<u32(*)[P / 2]>(&v[0]));
-          if (QUADS)
-            oem_sort_pk_half<P / 2, true>(
-                *reinterpret_cast<u32(*)[P / 2]>(&v2[0]));
-        } else {
-          oem_sort_pk_half<P / 2, false>(
-              *reinterpret_cast<u32(*)[P / 2]>(&v[P / 2]));
-          if (QUADS)
-            oem_sort_pk_half<P / 2, false>(
-                *reinterpret_cast<u32(*)[P / 2]>(&v2[P / 2]));
-        }
+        if (h == 0)
+          selnet::half_sort<P / 2, true, PkKeyU16>(selnet::half<0>(v));
+        else
+          selnet::half_sort<P / 2, false, PkKeyU16>(selnet::half<1>(v));
       }
-      pk_median_select<P>(v, sel_lo[0], sel_hi[0]);
-      if (QUADS)
-        pk_median_select<P>(*reinterpret_cast<u32(*)[P]>(&v2[0]),
-                            sel_lo[1], sel_hi[1]);
+      selnet::median_select<P, PkKeyU16>(v, sel_lo, sel_hi);
     } else {
 #pragma unroll
-      for (int i = 0; i < P; ++i) {
-        v[i] = pk_key_from_bf16(v[i]);
-        if (QUADS) v2[i] = pk_key_from_bf16(v2[i]);
-      }
+      for (int i = 0; i < P; ++i) v[i] = pk_key_from_bf16(v[i]);
       if (n < P) {
 #pragma unroll
         for (int i = 0; i < P; ++i)
-          if (i >= nv) {
-            v[i] = 0xFFFFFFFFu;
-            if (QUADS) v2[i] = 0xFFFFFFFFu;
-          }
+          if (i >= nv) v[i] = 0xFFFFFFFFu;
       }
-      bitonic_sort_pk<P>(v);
-      if (QUADS) bitonic_sort_pk<P>(*reinterpret_cast<u32(*)[P]>(&v2[0]));
+      selnet::bitonic_sort<P, PkKeyU16>(v);
     }
     const int plo = vecify((n - 1) >> 1), phi = vecify(n >> 1);
     const int fv = vecify(f), nfv = vecify(n - f);
     u32* outw = reinterpret_cast<u32*>(out);
+    // One trip: the loop is what is left of the retired four-column variant,
+    // which ran it once per packed pair. As straight-line code 10 of the
+    // TRIMMED and MEAMED instantiations come out scheduled differently
+    // (profiles/r06_colsel_networks.md), so it stays until a change that is
+    // measured, not only compared, takes it out.
 #pragma unroll
-    for (int half = 0; half < (QUADS ? 2 : 1); ++half) {
-      const u32* arr = half ? v2 : v;
+    for (int half = 0; half < 1; ++half) {
       float m0, m1;
       if (MODE == MEDIAN) {
-        const u32 lo = sel_lo[half];
-        const u32 hi = (n & 1) ? lo : sel_hi[half];
+        const u32 lo = sel_lo;
+        const u32 hi = (n & 1) ? lo : sel_hi;
         m0 = 0.5f * (key_to_float(lo & 0xFFFFu) + key_to_float(hi & 0xFFFFu));
         m1 = 0.5f * (key_to_float(lo >> 16) + key_to_float(hi >> 16));
       } else if (MODE == TRIMMED) {
@@ -657,8 +461,8 @@ colsel_pk_median_bf16(const unsigned short* __restrict__ X,
 #pragma unroll
         for (int i = 0; i < P; ++i)
           if (i >= fv && i < nfv) {
-            s0 += key_to_float(arr[i] & 0xFFFFu);
-            s1 += key_to_float(arr[i] >> 16);
+            s0 += key_to_float(v[i] & 0xFFFFu);
+            s1 += key_to_float(v[i] >> 16);
           }
         const float inv = 1.0f / (float)(n - 2 * f);
         m0 = s0 * inv;
@@ -676,21 +480,21 @@ colsel_pk_median_bf16(const unsigned short* __restrict__ X,
         const int roff = vecify(2 * f + 2 - n);  // maps [n-f-1, n) -> [f+1, 2f+2)
 #pragma unroll
         for (int i = 0; i < P; ++i) {
-          if (i <= fv) strip[i] = arr[i];
-          if (i >= nv - fv - 1 && i < nv) strip[i + roff] = arr[i];
+          if (i <= fv) strip[i] = v[i];
+          if (i >= nv - fv - 1 && i < nv) strip[i + roff] = v[i];
         }
         u32 mlo = 0, mhi = 0;
 #pragma unroll
         for (int i = 0; i < P; ++i) {
-          if (i == plo) mlo = arr[i];
-          if (i == phi) mhi = arr[i];
+          if (i == plo) mlo = v[i];
+          if (i == phi) mhi = v[i];
         }
         float t0 = 0.0f, t1 = 0.0f;
 #pragma unroll
         for (int i = 0; i < P; ++i)
           if (i < nv) {
-            t0 += key_to_float(arr[i] & 0xFFFFu);
-            t1 += key_to_float(arr[i] >> 16);
+            t0 += key_to_float(v[i] & 0xFFFFu);
+            t1 += key_to_float(v[i] >> 16);
           }
 #pragma unroll
         for (int half2 = 0; half2 < 2; ++half2) {
@@ -720,7 +524,7 @@ colsel_pk_median_bf16(const unsigned short* __restrict__ X,
       c1.h = __float2bfloat16(m1);
       o.s[0] = c0.s;
       o.s[1] = c1.s;
-      if (!ROWS || unit < nunits) outw[pair + half] = o.w;
+      if (!ROWS || unit < npairs) outw[pair + half] = o.w;
     }
   }
 }
@@ -927,8 +731,7 @@ median_gram_bf16_kernel(const unsigned short* __restrict__ X,
   for (int e = 0; e < MG_TILES; ++e) acc[e] = mg_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 
   const int nv = vecify(n);
-  // MEDIAN pad split, as in colsel_pk_median_bf16
-  const int n_lo = vecify(n + (P / 2 - 1 - ((n - 1) >> 1)));
+  const int n_lo = vecify(selnet::median_pad_split<P>(n));
 
   // loads of strip s, per lane clamped to the row's last pair. A strip past
   // the end is never used: the wave reads `own` (in range) again instead,
@@ -1024,12 +827,8 @@ median_gram_bf16_kernel(const unsigned short* __restrict__ X,
       }
       ops += k;
     };
-    oem_sort_pk_half<P / 2, true, PkRawF16>(
-        *reinterpret_cast<u32(*)[P / 2]>(&v[0]), tick);
-    oem_sort_pk_half<P / 2, false, PkRawF16>(
-        *reinterpret_cast<u32(*)[P / 2]>(&v[P / 2]), tick);
     u32 lo, hi;
-    pk_median_select<P, PkRawF16>(v, lo, hi, tick);
+    selnet::median_network<P, PkRawF16>(v, lo, hi, tick);
     // whatever the network did not reach (nothing, with the constants above)
 #pragma unroll
     for (int k = 0; k < MG_EVENTS; ++k) {
@@ -1304,24 +1103,9 @@ void launch_colsel<__hip_bfloat16>(const __hip_bfloat16* X,
                                    int n_src, hipStream_t stream) {
   if (n <= 64 && (d % 2) == 0) {
     const int block = 256;
-    // A/B'd on MI355X: QUADS (8 B/lane) TIED the old full-sort variant
-    // (3.9 vs 3.8 ms at 64 x 125M) and LOSES 3x to the selection-network
-    // pair variant (9.09 vs 3.09 ms — two 64-reg key arrays force the
-    // 3-waves/SIMD bound while the pair kernel runs at 5). Single-pair
-    // is the shipping path; BYZPY_PK_QUADS=1 re-runs the comparison.
     const int grid = capped_grid(d >> 1, block);
     const unsigned short* Xu = reinterpret_cast<const unsigned short*>(X);
     unsigned short* Ou = reinterpret_cast<unsigned short*>(out);
-    // A/B aid: BYZPY_PK_QUADS=1 re-measures the 4-column (8 B/lane)
-    // MEDIAN variant (tied pre-selection-network; see the comment above)
-    if (rows == nullptr && mode == MEDIAN && n > 32 && (d % 4) == 0 &&
-        std::getenv("BYZPY_PK_QUADS") != nullptr) {
-      const int qgrid = capped_grid(d >> 2, block);
-      hipLaunchKernelGGL((colsel_pk_median_bf16<64, true, MEDIAN, false>),
-                         dim3(qgrid), dim3(block), 0, stream, Xu, Ou, n, d, f,
-                         rows, n_src, (const float*)nullptr);
-      return;
-    }
     by_mode(mode, [&](auto m) {
       constexpr int MODE = decltype(m)::value;
       // MEAMED stages a 2(f+1)-key strip per thread in LDS (odd stride)
@@ -1331,7 +1115,7 @@ void launch_colsel<__hip_bfloat16>(const __hip_bfloat16* X,
         constexpr bool ROWS = decltype(r)::value;
         by_reg_width(n, [&](auto p) {
           hipLaunchKernelGGL(
-              (colsel_pk_median_bf16<decltype(p)::value, false, MODE, ROWS>),
+              (colsel_pk_median_bf16<decltype(p)::value, MODE, ROWS>),
               dim3(grid), dim3(block), lds, stream, Xu, Ou, n, d, f, rows,
               n_src, (const float*)nullptr);
         });
@@ -1377,7 +1161,7 @@ void launch_median_gram_bf16(const __hip_bfloat16* X, __hip_bfloat16* med,
   // has nothing to do costs a few microseconds.
   const long gwant = (long)capped_grid(d >> 1, 256);
   const long gcap = 4L * cus;
-  hipLaunchKernelGGL((colsel_pk_median_bf16<64, false, MEDIAN, false, true>),
+  hipLaunchKernelGGL((colsel_pk_median_bf16<64, MEDIAN, false, true>),
                      dim3((unsigned)(gwant < gcap ? gwant : gcap)), dim3(256),
                      0, stream, reinterpret_cast<const unsigned short*>(X),
                      reinterpret_cast<unsigned short*>(med), n, d, 0,

@@ -3,9 +3,10 @@
 // The schedule only names WHICH pairs are compare-exchanged, in which
 // order; what a compare-exchange does is the caller's functor
 //   ce(lo, hi):  afterwards element lo holds the smaller, hi the larger.
-// colsel.hip instantiates it on packed-u16 keys (v_pk_min/max_u16) and on
-// f32 registers; tests/oem_sort_check.cpp instantiates it on host arrays
-// and proves it by the 0-1 principle. Every loop bound is a constant once
+// selnet.h's half_sort instantiates it for the kernels of colsel.hip (f32
+// registers, packed u16 keys, packed raw bf16 words);
+// tests/oem_sort_check.cpp instantiates it on host arrays and proves it by
+// the 0-1 principle. Every loop bound is a constant once
 // the enclosing loops are unrolled, so on the device all indices are
 // compile-time and the element array stays in registers.
 //

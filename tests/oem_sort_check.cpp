@@ -9,6 +9,18 @@
 //                      it; 2^32 inputs are out of reach, a sample is run on
 //                      top;
 //   counts:            191 compare-exchanges for 32 inputs, 63 for 16.
+//
+// and of the networks built on it in byzpy_amd/hip/csrc/selnet.h, on int
+// arrays with an integer min/max policy, for P = 8, 16, 32, 64:
+//   median_select:     every [ascending 0-1 half | descending 0-1 half],
+//                      (P/2 + 1)^2 inputs: mlo / mhi are ranks P/2-1 / P/2
+//                      (0-1 principle: all inputs of that shape);
+//   whole median path: every n in 1..P on n values of 3 levels, every
+//                      count-split of the levels, in a fixed and in the
+//                      reversed arrangement, padded at median_pad_split,
+//                      through median_network: the median of the n values;
+//   bitonic_sort:      every 0-1 input for P <= 16, for larger P every 0-1
+//                      input that is constant on aligned runs of P / 16.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -17,6 +29,7 @@
 #include <vector>
 
 #include "oem_sort.h"
+#include "selnet.h"
 
 namespace {
 
@@ -147,6 +160,101 @@ long count_ces() {
   return ce.count;
 }
 
+struct IntMinMax {
+  static int mn(int a, int b) { return std::min(a, b); }
+  static int mx(int a, int b) { return std::max(a, b); }
+};
+
+template <int P>
+void median_select_all_01_halves() {
+  bool ok = true;
+  for (int za = 0; za <= P / 2; ++za)
+    for (int zb = 0; zb <= P / 2; ++zb) {
+      int v[P], ref[P];
+      for (int i = 0; i < P / 2; ++i) {
+        v[i] = i >= za;               // ascending: za zeros first
+        v[P / 2 + i] = i < P / 2 - zb;  // descending: zb zeros last
+      }
+      std::copy(v, v + P, ref);
+      std::sort(ref, ref + P);
+      int mlo = -1, mhi = -1;
+      selnet::median_select<P, IntMinMax>(v, mlo, mhi);
+      ok = ok && mlo == ref[P / 2 - 1] && mhi == ref[P / 2];
+    }
+  char what[80];
+  std::snprintf(what, sizeof what,
+                "median_select<%d> over %d x %d sorted 0-1 halves", P,
+                P / 2 + 1, P / 2 + 1);
+  expect(ok, what);
+}
+
+// n real values of levels 1, 2, 3 (c1, c2, n - c1 - c2 of each), laid out by
+// a fixed scatter or its reverse; pads 0 below and 4 above, split where the
+// kernels split them
+template <int P>
+void median_path_all_n() {
+  bool ok = true;
+  long cases = 0;
+  for (int n = 1; n <= P; ++n) {
+    const int n_lo = selnet::median_pad_split<P>(n);
+    ok = ok && n_lo >= n && n_lo <= P;
+    for (int c1 = 0; c1 <= n; ++c1)
+      for (int c2 = 0; c1 + c2 <= n; ++c2)
+        for (int rev = 0; rev < 2; ++rev) {
+          int real[P], v[P];
+          for (int i = 0; i < n; ++i) {
+            // 37 is coprime to every n <= 64 but 37 itself
+            const int slot = n == 37 ? i : (int)((37L * i + 11) % n);
+            real[rev ? n - 1 - slot : slot] = i < c1 ? 1 : (i < c1 + c2 ? 2 : 3);
+          }
+          for (int i = 0; i < P; ++i) v[i] = i < n ? real[i] : (i < n_lo ? 0 : 4);
+          std::sort(real, real + n);
+          int mlo = -1, mhi = -1;
+          selnet::median_network<P, IntMinMax>(v, mlo, mhi);
+          if (n & 1) mhi = mlo;  // as the kernels do
+          ok = ok && mlo == real[(n - 1) >> 1] && mhi == real[n >> 1];
+          ++cases;
+        }
+  }
+  char what[80];
+  std::snprintf(what, sizeof what,
+                "median_network<%d>: median of n = 1..%d padded values (%ld cases)",
+                P, P, cases);
+  expect(ok, what);
+}
+
+template <int P>
+void bitonic_sort_01_runs() {
+  constexpr int RUN = P <= 16 ? 1 : P / 16, BITS = P / RUN;
+  bool ok = true;
+  for (uint32_t bits = 0; bits < (1u << BITS); ++bits) {
+    int v[P], ones = 0;
+    for (int i = 0; i < P; ++i) ones += v[i] = (bits >> (i / RUN)) & 1;
+    selnet::bitonic_sort<P, IntMinMax>(v);
+    int after = 0;
+    for (int i = 0; i < P; ++i) after += v[i];
+    ok = ok && after == ones && is_sorted_dir<P, true>(v);
+  }
+  char what[96];
+  std::snprintf(what, sizeof what,
+                "bitonic_sort<%d> over all 0-1 inputs constant on runs of %d",
+                P, RUN);
+  expect(ok, what);
+}
+
+template <int P>
+void selnet_checks() {
+  median_select_all_01_halves<P>();
+  median_path_all_n<P>();
+  bitonic_sort_01_runs<P>();
+  // half<H> is a view, extract_at a read
+  int v[P];
+  for (int i = 0; i < P; ++i) v[i] = 100 + i;
+  bool ok = &selnet::half<0>(v)[0] == &v[0] && &selnet::half<1>(v)[0] == &v[P / 2];
+  for (int i = 0; i < P; ++i) ok = ok && selnet::extract_at(v, i) == 100 + i;
+  expect(ok, "half<H> views v in place, extract_at(v, i) is v[i]");
+}
+
 }  // namespace
 
 int main() {
@@ -163,6 +271,12 @@ int main() {
   expect(count_ces<32>() == 191, "191 compare-exchanges for 32 inputs");
   expect(count_ces<16>() == 63, "63 compare-exchanges for 16 inputs");
   expect(count_ces<8>() == 19, "19 compare-exchanges for 8 inputs");
+  selnet_checks<8>();
+  selnet_checks<16>();
+  selnet_checks<32>();
+  selnet_checks<64>();
+  std::printf("bitonic_sort: exhaustive 0-1 inputs (runs of P / 16 past P = 16), "
+              "not sampled permutations\n");
   if (failures == 0) std::printf("oem_sort_check: all checks passed\n");
   return failures == 0 ? 0 : 1;
 }

@@ -13,15 +13,10 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from byzpy_amd import hip
+from _median_gram_cases import ext, fused, gram_bound, gram_ref  # noqa: F401
 from byzpy_amd.hip import dispatch as D
 
 TILE_COLS = 512  # columns per tile of the fused kernel
-
-
-@pytest.fixture(scope="module")
-def ext():
-    return hip.require()
 
 
 def _rand(n, d, seed):
@@ -33,32 +28,14 @@ def _rand(n, d, seed):
     return X.to("cuda", torch.bfloat16)
 
 
-def _gram_ref(X):
-    Xd = X.cpu().double()
-    return Xd @ Xd.T
-
-
-def _gram_bound(G_ref):
-    return 0.3 * max(1.0, float(G_ref.abs().max()) / 100)
-
-
-def _fused(ext, X, G=None):
-    n = X.shape[0]
-    if G is None:
-        # garbage, not zeros: the call has to overwrite it
-        G = torch.full((n, n), 1.0e9, dtype=torch.float32, device=X.device)
-    med = ext.colsel(X, 0, 0, gram=G)
-    return med, G
-
-
 def _check(ext, X):
-    med, G = _fused(ext, X)
-    G_ref = _gram_ref(X)
+    med, G = fused(ext, X)
+    G_ref = gram_ref(X)
     err = (G.cpu().double() - G_ref).abs().max().item()
     print(f"n={X.shape[0]} d={X.shape[1]} gram err {err:.4g} "
-          f"bound {_gram_bound(G_ref):.4g}")
+          f"bound {gram_bound(G_ref):.4g}")
     assert torch.equal(med, ext.colsel(X, 0, 0))
-    assert err < _gram_bound(G_ref)
+    assert err < gram_bound(G_ref)
     return G, G_ref
 
 
@@ -83,20 +60,20 @@ def test_inf_rows_keep_the_median_bits(ext):
     X = _rand(64, 8192, seed=11)
     X[3] = float("inf")
     X[5] = float("-inf")
-    med, _ = _fused(ext, X)
+    med, _ = fused(ext, X)
     assert torch.equal(med, ext.colsel(X, 0, 0))
 
 
 def test_gram_is_overwritten_not_accumulated(ext):
     X = _rand(48, 1022, seed=5)
-    G_ref = _gram_ref(X)
-    _, G = _fused(ext, X)
+    G_ref = gram_ref(X)
+    _, G = fused(ext, X)
     first = G.clone()
-    _fused(ext, X, G)
+    fused(ext, X, G)
     diff = (G - first).abs().max().item()
-    print(f"second call differs by {diff:.4g}, bound {_gram_bound(G_ref):.4g}")
-    assert diff < _gram_bound(G_ref)
-    assert (G.cpu().double() - G_ref).abs().max().item() < _gram_bound(G_ref)
+    print(f"second call differs by {diff:.4g}, bound {gram_bound(G_ref):.4g}")
+    assert diff < gram_bound(G_ref)
+    assert (G.cpu().double() - G_ref).abs().max().item() < gram_bound(G_ref)
 
 
 def test_split_toggle_gives_the_same_median(monkeypatch):
@@ -108,9 +85,9 @@ def test_split_toggle_gives_the_same_median(monkeypatch):
     monkeypatch.setenv("BYZPY_MEDIAN_GRAM", "split")
     med_split, G_split = D.median_and_gram(X)
     assert torch.equal(med_fused, med_split)
-    G_ref = _gram_ref(X)
+    G_ref = gram_ref(X)
     for G in (G_fused, G_split):
-        assert (G.cpu().double() - G_ref).abs().max().item() < _gram_bound(G_ref)
+        assert (G.cpu().double() - G_ref).abs().max().item() < gram_bound(G_ref)
 
 
 @pytest.mark.parametrize(
@@ -123,10 +100,10 @@ def test_keyword_means_the_same_where_the_fused_kernel_does_not_apply(
 ):
     g = torch.Generator().manual_seed(n + d)
     X = torch.randn(n, d, generator=g).to("cuda", dtype)
-    med, G = _fused(ext, X)
+    med, G = fused(ext, X)
     assert torch.equal(med, ext.colsel(X, 0, 0))
-    G_ref = _gram_ref(X)
-    assert (G.cpu().double() - G_ref).abs().max().item() < _gram_bound(G_ref)
+    G_ref = gram_ref(X)
+    assert (G.cpu().double() - G_ref).abs().max().item() < gram_bound(G_ref)
 
 
 def test_bad_arguments_are_refused_by_name(ext):

@@ -27,7 +27,8 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from byzpy_amd import hip
+from _median_gram_cases import (ext, fused, gram_bound, gram_ref,  # noqa: F401
+                                 split)
 from byzpy_amd.hip.graphs import CapturedAggregate
 
 NS = [33, 48, 63, 64]
@@ -36,19 +37,6 @@ D_MULTI_CHUNK = 2 * 512 * 512 + 514
 
 LEGAL_MAG = 0x7C00      # magnitude bits of the legal patterns: [0, 0x7C00)
 IN_RANGE_MAG = 0x5880   # 2^50: d * 2^100 stays finite in f32 for d < 2^28
-
-
-@pytest.fixture(scope="module")
-def ext():
-    return hip.require()
-
-
-@pytest.fixture(params=["even", "ticket"])
-def split(request, monkeypatch):
-    """strips as one even share per wave, or drawn from the work counter"""
-    monkeypatch.setenv("BYZPY_MEDIAN_GRAM_TICKET",
-                       "1" if request.param == "ticket" else "0")
-    return request.param
 
 
 def _i16(pattern):
@@ -73,13 +61,6 @@ def _patterns(mag_end, device="cuda"):
     return torch.cat([m, m | 0x8000])
 
 
-def _fused(ext, X):
-    n = X.shape[0]
-    G = torch.full((n, n), 1.0e9, dtype=torch.float32, device=X.device)
-    med = ext.colsel(X, 0, 0, gram=G)
-    return med, G
-
-
 def _assert_median_bits(ext, X, med):
     ref = ext.colsel(X, 0, 0)
     wrong = (_bits(med) != _bits(ref)).nonzero()
@@ -90,14 +71,9 @@ def _assert_median_bits(ext, X, med):
     )
 
 
-def _gram_ref(X):
-    Xd = X.cpu().double()
-    return Xd @ Xd.T
-
-
 def _assert_gram_within_bound(G, X):
-    G_ref = _gram_ref(X)
-    bound = 0.3 * max(1.0, float(G_ref.abs().max()) / 100)
+    G_ref = gram_ref(X)
+    bound = gram_bound(G_ref)
     err = (G.cpu().double() - G_ref).abs().max().item()
     print(f"n={X.shape[0]} d={X.shape[1]} gram err {err:.4g} bound {bound:.4g}")
     assert err < bound
@@ -167,7 +143,7 @@ def test_compare_exchange_semantics(ext, span, role):
     lo_fill, hi_fill = 0x8000 | (mag_end - 1), mag_end - 1
     X = _semantics_matrix(a, b, lo_fill, hi_fill, 30 if role == "max" else 31, g)
     assert X.shape[1] % 2 == 0
-    med, G = _fused(ext, X)
+    med, G = fused(ext, X)
     finite = bool(torch.isfinite(G.diagonal()).all())
     print(f"{span} {role}: {X.shape[1]} columns, Gram diagonal finite: {finite}")
     if span == "in_range":
@@ -203,7 +179,7 @@ def _uniform_patterns(n, d, mag_end, seed):
 def test_uniform_patterns(ext, split, span, n, d):
     mag_end = LEGAL_MAG if span == "full_range" else IN_RANGE_MAG
     X = _uniform_patterns(n, d, mag_end, seed=1000 * n + d)
-    med, G = _fused(ext, X)
+    med, G = fused(ext, X)
     if span == "in_range":
         assert bool(torch.isfinite(G.diagonal()).all())
     _assert_median_bits(ext, X, med)
@@ -213,7 +189,7 @@ def test_uniform_patterns(ext, split, span, n, d):
 def test_uniform_patterns_multi_chunk(ext, split, span):
     mag_end = LEGAL_MAG if span == "full_range" else IN_RANGE_MAG
     X = _uniform_patterns(64, D_MULTI_CHUNK, mag_end, seed=5)
-    med, G = _fused(ext, X)
+    med, G = fused(ext, X)
     if span == "in_range":
         assert bool(torch.isfinite(G.diagonal()).all())
     _assert_median_bits(ext, X, med)
@@ -249,7 +225,7 @@ def test_gaussian_with_signed_zeros(ext, split, n, d):
     X = _gauss_with_zeros(n, d, seed=7000 + 100 * n + d)
     assert bool((_bits(X) == _i16(0x8000)).any())  # -0 is there
     assert bool((_bits(X) == 0).any())
-    med, G = _fused(ext, X)
+    med, G = fused(ext, X)
     assert bool(torch.isfinite(G.diagonal()).all())
     _assert_median_bits(ext, X, med)
     _assert_gram_within_bound(G, X)
@@ -258,7 +234,7 @@ def test_gaussian_with_signed_zeros(ext, split, n, d):
 
 def test_gaussian_with_signed_zeros_multi_chunk(ext, split):
     X = _gauss_with_zeros(64, D_MULTI_CHUNK, seed=71)
-    med, G = _fused(ext, X)
+    med, G = fused(ext, X)
     assert bool(torch.isfinite(G.diagonal()).all())
     _assert_median_bits(ext, X, med)
     _assert_gram_within_bound(G, X)
@@ -268,8 +244,8 @@ def test_integer_data_gram_is_exact(ext, split):
     # the Gram side is untouched: integers in {-2..2} give exact sums
     g = torch.Generator().manual_seed(3)
     X = torch.randint(-2, 3, (48, 1022), generator=g).to("cuda", torch.bfloat16)
-    med, G = _fused(ext, X)
-    assert torch.equal(G.cpu().double(), _gram_ref(X))
+    med, G = fused(ext, X)
+    assert torch.equal(G.cpu().double(), gram_ref(X))
     _assert_median_bits(ext, X, med)
 
 
@@ -292,7 +268,7 @@ def test_one_illegal_word_falls_back(ext, n, where, what):
     X = X.to(torch.bfloat16)
     row, col = (2 * n) // 3, POSITIONS[where]
     _bits(X)[row, col] = _i16(ILLEGAL[what])
-    med, G = _fused(ext, X)
+    med, G = fused(ext, X)
     assert not bool(torch.isfinite(G[row, row]))
     _assert_median_bits(ext, X, med)
 
@@ -304,7 +280,7 @@ def test_legal_words_whose_gram_overflows(ext):
                          dtype=torch.int32)
     X = _bf16(0x5F00 | (sign << 15))
     assert float(X.float().abs().min()) == 2.0**63
-    med, G = _fused(ext, X)
+    med, G = fused(ext, X)
     assert bool(torch.isinf(G.diagonal()).all())
     _assert_median_bits(ext, X, med)
 
@@ -324,7 +300,7 @@ def test_graph_capture_and_replay(ext, split):
     for X in (Xa, Xb, Xa):
         med = cap.run(X).clone()
         G_replay = G.clone()
-        eager, G_eager = _fused(ext, X)
+        eager, G_eager = fused(ext, X)
         assert torch.equal(_bits(med), _bits(eager))
         assert torch.equal(torch.isfinite(G_replay), torch.isfinite(G_eager))
         assert bool(torch.isfinite(G_replay.diagonal()).all()) == (X is Xa)

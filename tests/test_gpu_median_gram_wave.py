@@ -21,7 +21,8 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from byzpy_amd import hip
+from _median_gram_cases import (ext, fused, gram_bound, gram_ref,  # noqa: F401
+                                 split)
 
 TILE_COLS = 512  # columns that one block of four waves takes at a time
 WAVE_COLS = 128  # columns of a strip
@@ -30,37 +31,8 @@ NS = [33, 48, 63, 64]
 DS = [2, 126, 128, 130, 510, 512, 514, 1022]
 
 
-@pytest.fixture(scope="module")
-def ext():
-    return hip.require()
-
-
-@pytest.fixture(params=["even", "ticket"])
-def split(request, monkeypatch):
-    """how the strips reach the waves: one even share each (what the binding
-    picks at these sizes) or chunks drawn from the work counter (what it
-    picks from 2^25 columns up), forced here so that the drawn loop runs at
-    test sizes"""
-    monkeypatch.setenv("BYZPY_MEDIAN_GRAM_TICKET",
-                       "1" if request.param == "ticket" else "0")
-    return request.param
-
-
-def _gram_ref(X):
-    Xd = X.cpu().double()
-    return Xd @ Xd.T
-
-
-def _fused(ext, X):
-    n = X.shape[0]
-    # garbage, not zeros: the call has to overwrite all of it
-    G = torch.full((n, n), 1.0e9, dtype=torch.float32, device=X.device)
-    med = ext.colsel(X, 0, 0, gram=G)
-    return med, G
-
-
 def _assert_exact(G, X):
-    G_ref = _gram_ref(X)
+    G_ref = gram_ref(X)
     assert float(G_ref.abs().max()) < 2.0**24
     Gd = G.cpu().double()
     wrong = (Gd != G_ref).nonzero()
@@ -95,7 +67,7 @@ def test_slab_ownership(ext, w):
     cols = slice(WAVE_COLS * w, WAVE_COLS * (w + 1))
     X[:, cols] = _int_matrix(64, WAVE_COLS, seed=40 + w)
     assert float(X[:, cols].abs().max()) == 2.0
-    med, G = _fused(ext, X)
+    med, G = fused(ext, X)
     _assert_exact(G, X)
     assert torch.equal(G, G.T)
     assert torch.equal(med, ext.colsel(X, 0, 0))
@@ -107,7 +79,7 @@ def test_k_slot_coverage(ext, n, d):
     # every column feeds at most four Gram entries, so a 16-byte slot that
     # is dropped or read twice shows up as a wrong count
     X = _two_rows_per_column(n, d)
-    med, G = _fused(ext, X)
+    med, G = fused(ext, X)
     _assert_exact(G, X)
     assert torch.equal(G, G.T)
     assert torch.equal(med, ext.colsel(X, 0, 0))
@@ -117,7 +89,7 @@ def test_k_slot_coverage(ext, n, d):
 @pytest.mark.parametrize("d", DS)
 def test_dense_integer_data(ext, split, n, d):
     X = _int_matrix(n, d, seed=1000 * n + d)
-    med, G = _fused(ext, X)
+    med, G = fused(ext, X)
     _assert_exact(G, X)
     assert torch.equal(G, G.T)
     assert torch.equal(med, ext.colsel(X, 0, 0))
@@ -130,7 +102,7 @@ def test_many_tiles_per_block_with_partial_last_tile(ext, split):
     # past the end. The last strip is partial (one full lane, tail lanes).
     d = 2 * 512 * TILE_COLS + 514
     X = _int_matrix(64, d, seed=77, device="cuda")
-    med, G = _fused(ext, X)
+    med, G = fused(ext, X)
     _assert_exact(G, X)
     assert torch.equal(G, G.T)
     assert torch.equal(med, ext.colsel(X, 0, 0))
@@ -147,7 +119,7 @@ def test_drawn_chunks(ext, monkeypatch):
     monkeypatch.setenv("BYZPY_MEDIAN_GRAM_TICKET", "1")
     n, d = 64, 4_000_002
     X = _int_matrix(n, d, seed=78, device="cuda")
-    med, G = _fused(ext, X)
+    med, G = fused(ext, X)
     G_ref = torch.zeros(n, n, dtype=torch.float64, device="cuda")
     step = 500_000
     for c in range(0, d, step):
@@ -158,15 +130,15 @@ def test_drawn_chunks(ext, monkeypatch):
     assert torch.equal(G, G.T)
     monkeypatch.setenv("BYZPY_MEDIAN_GRAM_TICKET", "0")
     assert torch.equal(med, ext.colsel(X, 0, 0))
-    med_even, G_even = _fused(ext, X)
+    med_even, G_even = fused(ext, X)
     assert torch.equal(med_even, med)
     assert torch.equal(G_even, G)
 
 
 def test_two_calls_give_the_same_bits(ext, split):
     X = _int_matrix(64, 4 * TILE_COLS + 130, seed=9)
-    med1, G1 = _fused(ext, X)
-    med2, G2 = _fused(ext, X)
+    med1, G1 = fused(ext, X)
+    med2, G2 = fused(ext, X)
     assert torch.equal(G1, G2)
     assert torch.equal(med1, med2)
     _assert_exact(G1, X)
@@ -178,9 +150,9 @@ def test_random_data(ext, split):
     X = torch.randn(n, d, generator=g)
     X *= (1.0 + torch.arange(n, dtype=torch.float32) / n)[:, None]
     X = X.to("cuda", torch.bfloat16)
-    med, G = _fused(ext, X)
-    G_ref = _gram_ref(X)
-    bound = 0.3 * max(1.0, float(G_ref.abs().max()) / 100)
+    med, G = fused(ext, X)
+    G_ref = gram_ref(X)
+    bound = gram_bound(G_ref)
     err = (G.cpu().double() - G_ref).abs().max().item()
     print(f"n={n} d={d} gram err {err:.4g} bound {bound:.4g}")
     assert err < bound
