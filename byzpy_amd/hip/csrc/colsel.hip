@@ -330,6 +330,20 @@ DEV u32 pk_key_from_bf16(u32 bits) {
   return bits ^ (t | 0x80008000u);
 }
 
+// the inverse, two lanes at once: non-negative values (key bit 15 set) drop
+// the bit, negative ones are complemented. 4 VALU; a bf16 word is the upper
+// half of its f32, so a raw word then unpacks with one shift or mask where a
+// key takes key_to_float's select per half.
+DEV u32 pk_bf16_from_key(u32 key) {
+  u32 t;
+  asm("v_pk_ashrrev_i16 %0, %2, %1"
+      : "=v"(t)
+      : "v"(key), "v"(0x000F000Fu));
+  return key ^ (~t | 0x80008000u);
+}
+DEV float pk_lo_float(u32 w) { return __uint_as_float(w << 16); }
+DEV float pk_hi_float(u32 w) { return __uint_as_float(w & 0xFFFF0000u); }
+
 DEV float key_to_float(u32 key16) {
   unsigned short bits =
       (key16 & 0x8000u) ? (unsigned short)(key16 ^ 0x8000u)
@@ -470,10 +484,14 @@ colsel_pk_median_bf16(const unsigned short* __restrict__ X,
       } else {  // MEAMED: per half, shrink the sorted window [l, r) from
         // whichever end deviates more from the median. The walk only ever
         // touches positions [0, f] and [n-f-1, n), so those 2(f+1) sorted
-        // keys are staged into a per-thread LDS strip and each step reads
+        // words are staged into a per-thread LDS strip and each step reads
         // its two candidate ends by dynamic ds_read in O(1) — the previous
         // O(P) predicated extract per step cost ~f*P*4 VALU ops per column
         // pair and left the kernel 4x slower than MEDIAN.
+        // Sorted, the keys have done their work: back to raw bf16 words
+        // once, so that every unpack below is one shift or mask.
+#pragma unroll
+        for (int i = 0; i < P; ++i) v[i] = pk_bf16_from_key(v[i]);
         extern __shared__ __attribute__((aligned(16))) u32 pk_lds[];
         const int stride_l = 2 * (f + 1) + 1;  // odd => spread banks
         u32* strip = pk_lds + (int)threadIdx.x * stride_l;
@@ -489,34 +507,60 @@ colsel_pk_median_bf16(const unsigned short* __restrict__ X,
           if (i == plo) mlo = v[i];
           if (i == phi) mhi = v[i];
         }
+        // The sums only ever ADD kept values, never a dropped one: a dropped
+        // Byzantine +-inf in a sum-then-subtract total leaves inf - inf, and
+        // +-1e30 has absorbed every honest value before it is taken out
+        // again. The core [f, n-f) is kept whatever the walk decides (empty
+        // for 2f >= n) and is summed from the registers; the ends are added
+        // from the strip once the walk has fixed the window.
         float t0 = 0.0f, t1 = 0.0f;
 #pragma unroll
         for (int i = 0; i < P; ++i)
-          if (i < nv) {
-            t0 += key_to_float(v[i] & 0xFFFFu);
-            t1 += key_to_float(v[i] >> 16);
+          if (i >= fv && i < nfv) {
+            t0 += pk_lo_float(v[i]);
+            t1 += pk_hi_float(v[i]);
           }
+        int wl[2], wr[2];  // the kept window [wl, wr) of either half
 #pragma unroll
         for (int half2 = 0; half2 < 2; ++half2) {
-          const int sh = half2 * 16;
-          const float med =
-              0.5f * (key_to_float((mlo >> sh) & 0xFFFFu) +
-                      key_to_float((mhi >> sh) & 0xFFFFu));
-          // running total: full first-n sum minus the dropped end each step
-          float total = half2 ? t1 : t0;
+          auto val = [&](u32 w) {
+            return half2 ? pk_hi_float(w) : pk_lo_float(w);
+          };
+          const float med = 0.5f * (val(mlo) + val(mhi));
           int l = vecify(0), r = nv;
           for (int kdrop = 0; kdrop < f; ++kdrop) {
-            const float vl = key_to_float((strip[l] >> sh) & 0xFFFFu);
-            const float vr =
-                key_to_float((strip[r - 1 + roff] >> sh) & 0xFFFFu);
+            const float vl = val(strip[l]);
+            const float vr = val(strip[r - 1 + roff]);
             const bool drop_left = (med - vl) > (vr - med);
-            total -= drop_left ? vl : vr;
             l += drop_left ? 1 : 0;
             r -= drop_left ? 0 : 1;
           }
-          const float m = total / (float)(n - f);
-          if (half2 == 0) m0 = m; else m1 = m;
+          wl[half2] = l;
+          wr[half2] = r;
         }
+        // The ends, one strip word of each side per trip (both halves share
+        // it): position j on the left, n-1-j on the right. The right side
+        // stops at max(f, n-f), where for 2f >= n the left side's [0, f)
+        // ends, so no position is taken twice. Selects, not products with
+        // a 0/1 mask: 0 * inf is NaN.
+        const int nright = vecify(min(f, n - f));
+        for (int j = 0; j < f; ++j) {
+          const u32 ws = strip[j];
+          const int pr = nv - 1 - j;
+          const u32 wd = strip[pr + roff];
+          const bool right = j < nright;
+          const bool kl0 = j >= wl[0] && j < wr[0];
+          const bool kl1 = j >= wl[1] && j < wr[1];
+          const bool kr0 = right && pr < wr[0];
+          const bool kr1 = right && pr < wr[1];
+          t0 += kl0 ? pk_lo_float(ws) : 0.0f;
+          t1 += kl1 ? pk_hi_float(ws) : 0.0f;
+          t0 += kr0 ? pk_lo_float(wd) : 0.0f;
+          t1 += kr1 ? pk_hi_float(wd) : 0.0f;
+        }
+        const float kept = (float)(n - f);
+        m0 = t0 / kept;
+        m1 = t1 / kept;
       }
       union { unsigned short s[2]; u32 w; } o;
       union { unsigned short s; __hip_bfloat16 h; } c0, c1;

@@ -373,6 +373,7 @@ def test_ps_engine_fuzz_on_device():
         # and the historically nastiest pairing: inf rows into order stats
         await one(CoordinateWiseTrimmedMean(f=2), InfAttack(), 99)
         await one(CoordinateWiseMedian(), InfAttack(), 100)
+        await one(MeanOfMedians(f=2), InfAttack(), 101)
 
     asyncio.run(main())
 

@@ -1,9 +1,10 @@
 """Seeded random-shape fuzz of the dispatch layer against the functional
 oracle (SURVEY.md §4 pattern: every HIP kernel numerics-tested against a
 plain torch fp32 reference). Shapes are drawn to cross every dispatch
-boundary: register kernels (n<=64, all pad counts), LDS sort (65..512 at
-small d), the rsel radix engine (large d), odd/even d (packed pair vs
-scalar bf16 path), and both dtypes."""
+boundary these sizes can reach: register kernels (n<=64, many pad counts),
+LDS sort (65..512), odd/even d (packed pair vs scalar bf16 path), and both
+dtypes. With n <= 512 and d < 5003 no shape here reaches the rsel radix
+engine (n > 512, or n > 64 at d >= 32768): test_gpu_colsel_exact.py does."""
 import pytest
 import torch
 

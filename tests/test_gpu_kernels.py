@@ -325,9 +325,13 @@ def test_every_preagg_on_device(preagg_name):
 
 
 class TestRadixMedianLargeN:
-    """bf16 median for n > 64: 2-pass streaming radix select vs fp32 oracle.
-    bf16 keys are exact (finite bf16 set), so the median of bf16 inputs
-    equals the oracle's median of the same values exactly."""
+    """bf16 median for n > 64 vs the fp32 oracle, bit for bit: a median of
+    bf16 inputs is one of them or the mean of two. The binding sends a
+    shape to the radix engine (rsel.hip) only for n > 512, or n > 64 at
+    d >= 32768, so at these d only n = 700 and 4096 of test_parity reach it;
+    n = 65 ... 512 and the other three tests (n = 100, 300, 129) run the
+    cooperative LDS sort. test_gpu_colsel_exact.py::test_radix covers the
+    radix engine at 64 < n <= 512."""
 
     @pytest.mark.parametrize("n", [65, 100, 128, 257, 512, 700, 4096])
     def test_parity(self, n):
@@ -386,8 +390,13 @@ def _meamed_tie_avg_ref(Xf: torch.Tensor, f: int) -> torch.Tensor:
 
 
 class TestRadixLargeNModes:
-    """rsel.hip generic engine: TRIMMED / MEAMED / f32 MEDIAN at n > 192
-    (the LDS-sort path's collapse regime) vs the fp32 CPU oracle."""
+    """TRIMMED / MEAMED / f32 MEDIAN at n >= 200 vs the fp32 CPU oracle.
+    Every d here is below 32768, so under the binding's routing rule
+    (radix for n > 512, or n > 64 at d >= 32768) only n = 1024, 2048 and
+    4096 run the rsel.hip radix engine; n = 200 ... 512, and the inf-rows
+    and ties tests (n = 300, 256, 400), run the cooperative LDS sort.
+    test_gpu_colsel_exact.py::test_radix covers the engine's modes at
+    64 < n <= 512 and just above."""
 
     @pytest.mark.parametrize("n", [200, 300, 512, 1024, 4096])
     @pytest.mark.parametrize("dtype", DTYPES)

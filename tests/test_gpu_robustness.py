@@ -46,6 +46,21 @@ class TestBreakdownContainment:
             assert torch.isfinite(out).all()
             assert float(out.abs().max()) <= float(honest.abs().max()) + 1e-4
 
+    @pytest.mark.parametrize("d", [4096, 4097], ids=["even-d", "odd-d"])
+    def test_meamed_bounded_by_honest_scale_bf16(self, d):
+        # even d: the packed two-columns-per-lane kernel; odd d: the
+        # register kernel. The honest rows are the bf16 values the device sees.
+        for seed in range(4):
+            n, f = 24, 8
+            X, _ = _data(n, f, d, seed, dtype=torch.bfloat16)
+            Xc = X.float().cpu()
+            honest_max = float(Xc.abs().masked_fill(Xc.abs() > 1e29, 0.0).max())
+            out = D.mean_of_medians(X, f).float().cpu()
+            assert torch.isfinite(out).all()
+            # a mean of honest bf16 values, rounded to bf16: one unit
+            # roundoff (2^-8) above the largest of them at the most
+            assert float(out.abs().max()) <= honest_max * (1 + 2.0 ** -8)
+
     def test_multi_krum_selects_honest(self):
         for seed in range(4):
             n, f, d = 24, 7, 4096
