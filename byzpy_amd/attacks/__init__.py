@@ -1,6 +1,7 @@
 from byzpy_amd.attacks.base import Attack
 from byzpy_amd.attacks.ops import (
     AGRTailoredAttack,
+    CoordinateTailoredAttack,
     EmpireAttack,
     GaussianAttack,
     InfAttack,
@@ -24,4 +25,5 @@ __all__ = [
     "MinMaxAttack",
     "MinSumAttack",
     "AGRTailoredAttack",
+    "CoordinateTailoredAttack",
 ]

@@ -143,6 +143,38 @@ class AGRTailoredAttack(Attack):
         return to_like(out, like)
 
 
+class CoordinateTailoredAttack(Attack):
+    """Tailored attack on the coordinate-wise rules (Shejwalkar & Houmansadr
+    2021): the f Byzantine workers all send mu + gamma * p with the gamma
+    that moves ``agr`` ("trimmed-mean" or "median"), run on the honest
+    gradients plus those f copies, farthest from the honest mean."""
+
+    name = "attack/agr-coordinate"
+    uses_honest_grads = True
+
+    def __init__(
+        self,
+        f: int,
+        agr: str = "trimmed-mean",
+        *,
+        perturbation: str = "std",
+        chunk_size: int = 8192,
+    ) -> None:
+        if f < 1:
+            raise ValueError("f must be >= 1")
+        if agr not in F.AGR_COORD_RULES:
+            raise ValueError(f"agr must be one of {F.AGR_COORD_RULES}, got {agr!r}")
+        D._perturb_code(perturbation)  # ValueError on an unknown name
+        self.f = int(f)
+        self.agr = agr
+        self.perturbation = perturbation
+        self.chunk_size = int(chunk_size)
+
+    def apply(self, *, honest_grads: Any) -> Any:
+        X, like = self._stack(honest_grads)
+        return to_like(D.agr_coord(X, self.f, self.agr, self.perturbation), like)
+
+
 class GaussianAttack(Attack):
     """iid N(mu, sigma^2) noise vector; seedable for determinism."""
 

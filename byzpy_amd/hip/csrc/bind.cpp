@@ -210,6 +210,53 @@ torch::Tensor colsel(torch::Tensor X, int64_t mode, int64_t f,
   return out;
 }
 
+// colsel(X, mode, f, mu=, p=, gammas=): the objective of the coordinate-wise
+// tailored attack (colsel.hip). X holds the n <= 64 honest rows, f >= 1 is
+// the number of copies of mu + gamma p appended to every column, mode 0 the
+// median and mode 1 the f-trimmed mean of those n + f values. Returns the
+// f64 (T,) vector D[t] = sum_j (mu_j - A_j(gammas[t]))^2. mu is an input and
+// need not be X's column mean. Values that are not finite rank as
+// torch.sort ranks them (NaN last): D is non-finite where the rule keeps one.
+// No host sync.
+torch::Tensor colsel_objective(torch::Tensor X, int64_t mode, int64_t f,
+                               torch::Tensor mu, torch::Tensor p,
+                               torch::Tensor gammas) {
+  check_matrix(X);
+  TORCH_CHECK(mode == 0 || mode == 1,
+              "colsel(mu=, p=, gammas=): expected mode 0 (median) or 1 "
+              "(trimmed mean), got ", mode);
+  const int64_t n = X.size(0), d = X.size(1);
+  TORCH_CHECK(n >= 1 && n <= COORD_MAX_N, "colsel(mu=, p=, gammas=) supports ",
+              "1 <= n <= ", COORD_MAX_N, ", got ", n);
+  TORCH_CHECK(d >= 1, "colsel(mu=, p=, gammas=): expected d >= 1");
+  TORCH_CHECK(f >= 1 && f <= INT_MAX / 2 && (mode == 0 || f < n),
+              "colsel(mu=, p=, gammas=) needs f >= 1, and f < n for the "
+              "trimmed mean, got n=", n, ", f=", f);
+  TORCH_CHECK(mu.dim() == 1 && p.dim() == 1 && gammas.dim() == 1,
+              "mu, p, gammas: expected vectors");
+  check_f32_vector(mu, d, "mu");
+  check_f32_vector(p, d, "p");
+  const int64_t T = gammas.numel();
+  TORCH_CHECK(T >= 1 && T <= COORD_MAX_TRIALS, "gammas: expected 1 to ",
+              COORD_MAX_TRIALS, " values, got ", T);
+  check_f32_vector(gammas, T, "gammas");
+  TORCH_CHECK(mu.device() == X.device() && p.device() == X.device() &&
+                  gammas.device() == X.device(),
+              "mu, p, gammas: expected X's device");
+  const int blocks = coord_objective_blocks((long)d);
+  auto f64 = X.options().dtype(torch::kFloat64);
+  auto part = torch::empty({(int64_t)blocks * COORD_MAX_TRIALS}, f64);
+  auto out = torch::empty({T}, f64);
+  by_dtype(X, [&](auto tag) {
+    using T_ = TAG_T(tag);
+    launch_coord_objective<T_>(ptr<T_>(X), f32(mu), f32(p), f32(gammas),
+                               part.data_ptr<double>(), out.data_ptr<double>(),
+                               (int)n, (long)d, (int)mode, (int)f, (int)T,
+                               cur_stream());
+  });
+  return out;
+}
+
 torch::Tensor row_sqnorms(torch::Tensor X) {
   check_matrix(X);
   const int n = (int)X.size(0);
@@ -789,6 +836,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("X"), py::arg("mode"), py::arg("f"),
         py::arg("rows") = c10::nullopt, py::kw_only(),
         py::arg("gram") = c10::nullopt);
+  m.def("colsel", &colsel_objective,
+        "coordinate-wise tailored attack objective: f64 D per trial gamma",
+        py::arg("X"), py::arg("mode"), py::arg("f"), py::kw_only(),
+        py::arg("mu"), py::arg("p"), py::arg("gammas"));
   m.def("row_sqnorms", &row_sqnorms);
   m.def("row_center_sqdists", &row_center_sqdists);
   m.def("row_scale", &row_scale);

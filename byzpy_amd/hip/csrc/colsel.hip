@@ -1065,6 +1065,221 @@ colsel_lds_kernel(const T* __restrict__ X, T* __restrict__ out,
   }
 }
 
+// ---------------------------------------------------------------------------
+// Coordinate-wise tailored attack objective (n <= 64): for each of 32 trial
+// gammas, D_t = sum_j (mu_j - A_j(gamma_t))^2, where A_j is the median or the
+// f-trimmed mean of column j's n honest values plus f copies of
+// v = mu_j + gamma_t p_j. One pass over X for all trials: the honest column
+// is sorted ONCE in registers, ascending with +inf pads (s_1 <= .. <= s_n,
+// 1-based below), and a trial never sorts again.
+//
+//  - rank k of the attacked column is v clamped between two honest order
+//    statistics, max(s_{k-f}, min(v, s_k)) with s_i = -inf below 1 and +inf
+//    past n: the median (M = 0) reads two (odd n + f) or four of them per
+//    column and clamps per trial.
+//  - the trimmed mean (M > 0) keeps honest rank i iff
+//    (s_i < v ? i > f : i <= n - f). With m = min(f, n - f): ranks
+//    f < i <= n - f are always kept (summed once per column, in f64), ranks
+//    n - f < i <= f never, rank i <= m iff !(s_i < v), rank i > n - m iff
+//    s_i < v; the copies of v fill the n - f kept slots that the honest
+//    values leave. Per trial that is 2 M compare-selects, M >= m the
+//    kernel's tail width (a template argument: 4, 8, 16 or 32). Both tails
+//    are read at compile-time indices: the low one is v[0 .. m) as sorted,
+//    the high one comes top-aligned out of a barrel shift by P - n (six
+//    wave-uniform conditional moves of the array, none taken at n == P);
+//    slots m .. M hold -inf (low) and +inf (high), which no v keeps: the
+//    compares see v raised to -FLT_MAX at least (below). The trial loop is
+//    straight-line code with no wave-uniform guard in it: 32 x 2 M
+//    loop-invariant conditions would be hoisted into scalar mask pairs and
+//    spill.
+//
+// Values that are not finite follow the order torch.sort gives them, which
+// is what the oracle and the torch composition see: a NaN ranks above +inf.
+// A NaN in X is loaded as +inf (the min/max network would drop it), a NaN v
+// compares as +inf, and v = -inf (or an f64 v below the f32 range) compares
+// as -FLT_MAX, which ranks it below every finite value and level with an
+// honest -inf, whose place in the sum it takes with the same value. The
+// kept copies enter the sum as count x v in f64 with v as it is, so a kept
+// NaN or infinite copy makes D non-finite, and a dropped one does not.
+//
+// v, the clamp, the sum of the kept values and mu - A are f64 (the tails'
+// partial sums f32); (mu - A)^2 goes into one f64 accumulator per trial and
+// thread, 64 VGPRs that live through the whole column loop next to the 64
+// sort registers: the kernel is built for 2 waves per SIMD (256 VGPRs).
+// Reduction, the same bits on every run: lanes by shuffle, the block's four
+// waves through LDS in wave order, one f64 partial per (block, trial);
+// coord_objective_finish adds the blocks in index order. No atomics.
+// ---------------------------------------------------------------------------
+
+constexpr int COORD_THREADS = 256;
+constexpr int COORD_T = COORD_MAX_TRIALS;
+
+// sorted[idx] of the n real values for a runtime idx that may fall outside:
+// -inf below 0, +inf from n on (the pads of the sorted array, or past it)
+template <int P>
+DEV float coord_rank(const float (&v)[P], int idx) {
+  float r = idx < 0 ? -PAD : PAD;
+#pragma unroll
+  for (int i = 0; i < P; ++i)
+    if (i == idx) r = v[i];
+  return r;
+}
+
+DEV double coord_wave_sum(double x) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+  return x;
+}
+
+// gammas holds ntrials <= COORD_T values; the trials past them repeat the
+// last one and coord_objective_finish drops their sums
+template <int P, int M, typename T>
+__global__ void __launch_bounds__(COORD_THREADS, 2)
+coord_objective_kernel(const T* __restrict__ X, const float* __restrict__ mu,
+                       const float* __restrict__ p,
+                       const float* __restrict__ gammas,
+                       double* __restrict__ part, int n, long d, int f,
+                       int ntrials) {
+  double acc[COORD_T];
+#pragma unroll
+  for (int t = 0; t < COORD_T; ++t) acc[t] = 0.0;
+  // the trial values, padded to COORD_T with the last one, staged once
+  __shared__ float gam[COORD_T];
+  if (threadIdx.x < COORD_T)
+    gam[threadIdx.x] = gammas[min((int)threadIdx.x, ntrials - 1)];
+  __syncthreads();
+
+  const double inv_kept = 1.0 / (double)(n - f);
+  const long col0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (long col = col0; col < d; col += stride) {
+    float v[P];
+    T raw[P];
+    // pinned raw-load walk: see colsel_reg_kernel's load phase
+    const T* xp = X + col;
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+      raw[i] = *xp;
+      if (i + 1 < n) xp += d;
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    const float muc = mu[col], pc = p[col];
+    const int nv = vecify(n);
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+      const float x = to_f<T>(raw[i]);
+      v[i] = x == x ? x : PAD;  // NaN ranks last, as in torch.sort
+    }
+    if (n < P) {
+#pragma unroll
+      for (int i = 0; i < P; ++i)
+        if (i >= nv) v[i] = PAD;
+    }
+    // Batcher's network over all P slots (selnet's half_sort sorts whatever
+    // array it is given: 543 compare-exchanges at P = 64, bitonic 672)
+    selnet::half_sort<P, true, F32MinMax>(v);
+    const double mud = (double)muc, pd = (double)pc;
+    // opaque per column: the 32 LDS reads stay in the loop instead of
+    // holding 32 (converted: 64) registers through it
+    int g0 = 0;
+    asm volatile("" : "+v"(g0));
+
+    if constexpr (M == 0) {
+      // 0-based positions q1 <= q2 of the attacked column's middles; position
+      // q lies between honest sorted[q - f] and sorted[q]
+      const int q1 = (n + f - 1) >> 1, q2 = (n + f) >> 1;
+      const double lo1 = (double)coord_rank<P>(v, vecify(q1 - f));
+      const double hi1 = (double)coord_rank<P>(v, vecify(q1));
+      const double lo2 = (double)coord_rank<P>(v, vecify(q2 - f));
+      const double hi2 = (double)coord_rank<P>(v, vecify(q2));
+#pragma unroll
+      for (int t = 0; t < COORD_T; ++t) {
+        const double vt = fma((double)gam[g0 + t], pd, mud);
+        const double c1 = fmax(lo1, fmin(vt, hi1));
+        const double c2 = fmax(lo2, fmin(vt, hi2));
+        // q1 == q2 (odd n + f): c1 == c2 and the mean is c1, exactly
+        const double diff = mud - (c1 + c2) * 0.5;
+        acc[t] = fma(diff, diff, acc[t]);
+      }
+    } else {
+      // always-kept middle, 0-based [f, n - f) (empty for 2f >= n)
+      const int fv = vecify(f), nfv = vecify(n - f);
+      double mid = 0.0;
+#pragma unroll
+      for (int i = 0; i < P; ++i)
+        if (i >= fv && i < nfv) mid += (double)v[i];
+      const int mv = vecify(min(f, n - f));  // ranks per tail, <= M
+      float lo[M], hi[M];  // lo[j] = s_{1+j}, hi[j] = s_{n-j}, j < m
+#pragma unroll
+      for (int j = 0; j < M; ++j) lo[j] = j < mv ? v[j] : -PAD;
+      const int sh = P - n;
+#pragma unroll
+      for (int b = 1; b < P; b <<= 1) {
+        if (sh & b) {
+#pragma unroll
+          for (int i = P - 1; i >= b; --i) v[i] = v[i - b];
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < M; ++j) hi[j] = j < mv ? v[P - 1 - j] : PAD;
+#pragma unroll
+      for (int t = 0; t < COORD_T; ++t) {
+        const double vt = fma((double)gam[g0 + t], pd, mud);
+        // v as the compares see it: NaN as +inf, nothing below -FLT_MAX
+        // (the pads stay inert for every v; see the header)
+        const float vr = (float)vt;
+        const float vf = vr == vr ? fmaxf(vr, -__FLT_MAX__) : PAD;
+        float tail = 0.0f;
+        int honest = 0;  // kept tail values
+#pragma unroll
+        for (int j = 0; j < M; ++j) {
+          // selects, not products with a 0/1 mask: 0 * inf is NaN. (Rank
+          // 1 + j and rank n - j could share one v_med3_f32(lo, v, hi), but
+          // the copies of v would then add up in f32: count x v in f64
+          // keeps a single column's mu - A within the tests' bound.)
+          const bool kl = !(lo[j] < vf);
+          const bool kh = hi[j] < vf;
+          tail += kl ? lo[j] : 0.0f;
+          tail += kh ? hi[j] : 0.0f;
+          honest += (kl ? 1 : 0) + (kh ? 1 : 0);
+        }
+        // the n - f kept slots hold the middle's max(n - 2f, 0) values, the
+        // kept tail values and, for the rest, copies of v
+        const int copies = mv - honest;
+        const double vsum = copies > 0 ? (double)copies * vt : 0.0;
+        const double diff = mud - (mid + (double)tail + vsum) * inv_kept;
+        acc[t] = fma(diff, diff, acc[t]);
+      }
+    }
+  }
+
+  __shared__ double wsum[COORD_THREADS / 64][COORD_T];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int t = 0; t < COORD_T; ++t) {
+    const double s = coord_wave_sum(acc[t]);
+    if (lane == 0) wsum[wave][t] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < COORD_T) {
+    double s = wsum[0][threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < COORD_THREADS / 64; ++w) s += wsum[w][threadIdx.x];
+    part[(long)blockIdx.x * COORD_T + threadIdx.x] = s;
+  }
+}
+
+// out[t] = part[0][t] + part[1][t] + ... in block order; one thread per trial
+__global__ void coord_objective_finish(const double* __restrict__ part,
+                                       double* __restrict__ out, int nblocks,
+                                       int ntrials) {
+  const int t = threadIdx.x;
+  if (t >= ntrials) return;
+  double s = 0.0;
+  for (int b = 0; b < nblocks; ++b) s += part[(long)b * COORD_T + t];
+  out[t] = s;
+}
+
 // Turns the runtime mode / row count into the kernels' template arguments:
 // fn receives std::integral_constant<int, MODE> / <int, P>.
 template <typename F>
@@ -1211,3 +1426,33 @@ void launch_median_gram_bf16(const __hip_bfloat16* X, __hip_bfloat16* med,
                      reinterpret_cast<unsigned short*>(med), n, d, 0,
                      (const int*)nullptr, 0, (const float*)G);
 }
+
+// One objective launch plus the block-order sum. `part` holds
+// coord_objective_blocks(d) * COORD_MAX_TRIALS doubles of scratch. The
+// trimmed mean runs the narrowest tail width M in {4, 8, 16, 32} that holds
+// its min(f, n - f) <= n / 2 <= P / 2 ranks, and never one past P / 2.
+template <typename T>
+void launch_coord_objective(const T* X, const float* mu, const float* p,
+                            const float* gammas, double* part, double* out,
+                            int n, long d, int mode, int f, int ntrials,
+                            hipStream_t stream) {
+  const int blocks = coord_objective_blocks(d);
+  const int m = f < n - f ? f : n - f;
+  by_reg_width(n, [&](auto pw) {
+    constexpr int P = decltype(pw)::value;
+    auto go = [&](auto mw) {
+      constexpr int M = decltype(mw)::value <= P / 2 ? decltype(mw)::value : P / 2;
+      hipLaunchKernelGGL((coord_objective_kernel<P, M, T>), dim3(blocks),
+                         dim3(COORD_THREADS), 0, stream, X, mu, p, gammas,
+                         part, n, d, f, ntrials);
+    };
+    if (mode == MEDIAN) go(std::integral_constant<int, 0>{});
+    else if (m <= 4) go(std::integral_constant<int, 4>{});
+    else if (m <= 8) go(std::integral_constant<int, 8>{});
+    else if (m <= 16) go(std::integral_constant<int, 16>{});
+    else go(std::integral_constant<int, 32>{});
+  });
+  hipLaunchKernelGGL(coord_objective_finish, dim3(1), dim3(64), 0, stream,
+                     (const double*)part, out, blocks, ntrials);
+}
+INSTANTIATE_LAUNCHER(launch_coord_objective)

@@ -52,6 +52,29 @@ void launch_median_gram_bf16(const __hip_bfloat16* X, __hip_bfloat16* med,
                              float* G, unsigned long long* ticket, int n,
                              long d, hipStream_t stream);
 
+// colsel.hip: objective of the coordinate-wise tailored attack. For each of
+// the ntrials values of gammas, out[t] = sum_j (mu_j - A_j)^2 in f64, A_j the
+// median (mode 0) or f-trimmed mean (mode 1) of column j's n honest values
+// plus f copies of mu_j + gammas[t] p_j. 1 <= n <= COORD_MAX_N, 1 <= ntrials
+// <= COORD_MAX_TRIALS, f >= 1 and f < n in mode 1. One pass over X; the grid
+// is capped and strides, each block leaves one f64 partial per trial in
+// `part` (coord_objective_blocks(d) * COORD_MAX_TRIALS doubles of scratch)
+// and a second launch adds them in block order: bitwise repeatable, no
+// atomics. Non-finite values rank as torch.sort ranks them (NaN last).
+constexpr int COORD_MAX_N = 64;
+constexpr int COORD_MAX_TRIALS = 32;
+constexpr int COORD_MAX_BLOCKS = 1024;  // of 256 columns a trip
+inline int coord_objective_blocks(long d) {
+  const long want = (d + 255) / 256;
+  return (int)(want < COORD_MAX_BLOCKS ? (want > 0 ? want : 1)
+                                       : COORD_MAX_BLOCKS);
+}
+template <typename T>
+void launch_coord_objective(const T* X, const float* mu, const float* p,
+                            const float* gammas, double* part, double* out,
+                            int n, long d, int mode, int f, int ntrials,
+                            hipStream_t stream);
+
 // rsel.hip: streaming radix-select engine for large n, same modes.
 // `state` is caller-zeroed d*4 u32 scratch; `med` is a d-float scratch,
 // read only by mode 2 (may be null otherwise)

@@ -1114,6 +1114,206 @@ def agr_tailored(
     return torch.addcmul(mu, gamma, p).to(X.dtype)
 
 
+# Tailored attacks on the coordinate-wise rules (Shejwalkar & Houmansadr
+# 2021): f copies of m = mu + gamma p with the gamma that maximises
+# D(gamma) = sum_j (mu_j - A_j(gamma))^2, A_j the trimmed mean / median of
+# column j's n honest values plus the f copies. Unlike the selection rules
+# this objective is a sum over all d columns, so each trial gamma needs a pass
+# over X; the device kernel serves 32 trials with one pass: the honest column
+# is sorted once, rank k of the attacked column is max(s_{k-f}, min(v, s_k)),
+# and the trimmed mean keeps honest rank i iff (s_i < v ? i > f : i <= n - f).
+# The search is the fixed schedule written out in ops/functional.py, which
+# keeps its own text (explicit attacked matrix, a sort per trial).
+
+AGR_COORD_RULES = ("trimmed-mean", "median")
+# Row cap of colsel(X, mode, f, mu=, p=, gammas=) (COORD_MAX_N in
+# csrc/launchers.h) and its trials per launch (COORD_MAX_TRIALS).
+AGR_COORD_MAX_N = 64
+_AGR_COORD_POINTS = 32
+_AGR_COORD_ZOOMS = 2
+_AGR_COORD_MODES = {"median": _COLSEL_MEDIAN, "trimmed-mean": _COLSEL_TRIMMED}
+# The composition works on column chunks sized to keep its (T, 2m, chunk)
+# temporaries near this many elements.
+_AGR_COORD_CHUNK_ELEMS = 1 << 25
+
+
+def _agr_coord_objective_torch(X, mu, p, gammas, f: int, agr: str):
+    """The kernel's per-column arithmetic as batched torch ops in f64, a
+    column chunk at a time: any device, any float dtype, no host sync."""
+    n, d = X.shape
+    T = gammas.numel()
+    g = gammas.double().reshape(T, 1)
+    inf = float("inf")
+    m = min(f, n - f)
+    width = max(2 * m, 4) if agr == "trimmed-mean" else 4
+    chunk = max(256, _AGR_COORD_CHUNK_ELEMS // (T * width))
+    out = torch.zeros(T, dtype=torch.float64, device=X.device)
+    zero = torch.zeros((), dtype=torch.float64, device=X.device)
+    for c0 in range(0, d, chunk):
+        S = X[:, c0 : c0 + chunk].double().sort(dim=0).values
+        muc = mu[c0 : c0 + chunk].double()[None, :]
+        v = muc + g * p[c0 : c0 + chunk].double()[None, :]
+        if agr == "median":
+            # 0-based middle positions q of the n + f values; position q lies
+            # between the honest sorted[q - f] and sorted[q]
+            def rank(idx, fill):
+                if 0 <= idx < n:
+                    return S[idx][None, :]
+                return torch.full_like(muc, fill)
+
+            cl = []
+            for q in ((n + f - 1) // 2, (n + f) // 2):
+                lo = rank(q - f, -inf if q - f < 0 else inf)
+                hi = rank(q, inf)
+                # a NaN ranks last (torch.sort): the smaller of v and hi is
+                # NaN only if both are (fmin), the larger if either is
+                cl.append(torch.maximum(lo, torch.fmin(v, hi)))
+            A = (cl[0] + cl[1]) * 0.5
+        else:
+            mid = S[f : n - f].sum(dim=0)[None, :]  # always kept; empty: 0
+            lo, hi = S[:m][None, :, :], S[n - m :][None, :, :]
+            # in the compares a NaN v ranks last, as torch.sort has it
+            vt = torch.where(torch.isnan(v), torch.full_like(v, inf), v)[:, None, :]
+            kl, kh = ~(lo < vt), hi < vt
+            tail = torch.where(kl, lo, zero).sum(dim=1) + torch.where(
+                kh, hi, zero
+            ).sum(dim=1)
+            copies = m - (kl.sum(dim=1) + kh.sum(dim=1))
+            vsum = torch.where(copies > 0, copies * v, zero)
+            A = (mid + tail + vsum) / float(n - f)
+        diff = muc - A
+        out += (diff * diff).sum(dim=1)
+    return out
+
+
+def agr_coord_objective(
+    X: torch.Tensor,
+    mu: torch.Tensor,
+    p: torch.Tensor,
+    gammas: torch.Tensor,
+    f: int,
+    agr: str,
+) -> torch.Tensor:
+    """f64 (T,) vector D[t] = sum_j (mu_j - A_j(gammas[t]))^2 for the honest
+    rows X (n, d), given mu and p (d,) — mu need not be the column mean. On
+    device for f32 / bf16 X with n <= AGR_COORD_MAX_N: one kernel pass over X
+    per 32 trials. Otherwise, and on CPU, the same arithmetic as batched torch
+    ops. No host sync either way. Values that are not finite rank as
+    torch.sort ranks them (NaN above +inf) on both paths, as in the oracle:
+    D is non-finite where such a value, or a non-finite mu, is kept."""
+    n = X.shape[0]
+    f = int(f)
+    F.agr_coord_check(n, f, agr)
+    gammas = gammas.reshape(-1)
+    if (
+        _gpu(X)
+        and n <= AGR_COORD_MAX_N
+        and X.dtype in (torch.float32, torch.bfloat16)
+    ):
+        ops = _hip.require()
+        Xc = X.contiguous()
+        mu32, p32 = mu.float().contiguous(), p.float().contiguous()
+        g32 = gammas.to(device=X.device, dtype=torch.float32).contiguous()
+        parts = [
+            ops.colsel(
+                Xc, _AGR_COORD_MODES[agr], f, mu=mu32, p=p32,
+                gammas=g32[t0 : t0 + _AGR_COORD_POINTS],
+            )
+            for t0 in range(0, g32.numel(), _AGR_COORD_POINTS)
+        ]
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+    return _agr_coord_objective_torch(X, mu, p, gammas.to(X.device), f, agr)
+
+
+def agr_coord_gamma(
+    X: torch.Tensor,
+    mu: torch.Tensor,
+    p: torch.Tensor,
+    a: torch.Tensor,
+    c: torch.Tensor,
+    f: int,
+    agr: str,
+    gamma0=None,
+) -> torch.Tensor:
+    """0-dim gamma of the coordinate-wise tailored attack from the honest rows
+    and the statistics mu, p, a (n,), c () of ``attack_stats``: the schedule of
+    ops/functional.py (round 0 at 0 and gamma0 2^-15 .. gamma0 2^15, two zoom
+    rounds of 32 interior points) as device ops around three objective calls,
+    no host sync. The anchor gamma0 defaults to sqrt(max a / c), the Min-Sum
+    value, and gamma is then 0 when c = 0 or a statistic is not finite; with
+    ``gamma0=`` given a and c are not read (as in the oracle) and gamma is 0
+    when gamma0 is not finite. Either way gamma is 0 when no trial's D is
+    finite. Every trial is an f32 value, worked out in f64."""
+    f = int(f)
+    F.agr_coord_check(X.shape[0], f, agr)
+    dev = X.device
+    f64 = dict(device=dev, dtype=torch.float64)
+    zero = torch.zeros((), **f64)
+    ninf = torch.full((), -float("inf"), **f64)
+    if gamma0 is None:
+        a64, c64 = a.to(**f64), c.to(**f64).reshape(())
+        ok = (c64 > 0) & torch.isfinite(c64)
+        g0 = torch.sqrt(a64.max() / torch.where(ok, c64, torch.ones_like(c64)))
+    else:  # as in the oracle: a given anchor is taken as it is, a and c unread
+        g0 = torch.as_tensor(gamma0, **f64).reshape(())
+        ok = torch.ones((), dtype=torch.bool, device=dev)
+    g0 = g0.float().double()
+    ok = ok & torch.isfinite(g0)
+    g0 = torch.where(ok, g0, zero)
+
+    def better(D, g, best_D, best_g):
+        return torch.isfinite(D) & ((D > best_D) | ((D == best_D) & (g < best_g)))
+
+    def evaluate(trials, best_g, best_D):
+        """Best of the incumbent and the ascending trials."""
+        D = agr_coord_objective(X, mu, p, trials.float(), f, agr).double()
+        Dm = torch.where(torch.isfinite(D), D, ninf)
+        top = Dm.max()
+        # the first (smallest gamma) trial that reaches the round's maximum
+        k = torch.arange(trials.numel(), device=dev)
+        first = torch.where(Dm == top, k, torch.full_like(k, trials.numel())).min()
+        g = trials.index_select(0, first.clamp_max(trials.numel() - 1).reshape(1))
+        g = g.reshape(())
+        take = better(top, g, best_D, best_g)
+        return torch.where(take, g, best_g), torch.where(take, top, best_D)
+
+    geo = 2.0 ** torch.arange(-15, 16, **f64)
+    trials = torch.cat([zero[None], (g0 * geo).float().double()])
+    nodes = trials
+    best_g, best_D = zero, ninf
+    frac = torch.arange(1, _AGR_COORD_POINTS + 1, **f64)
+    for r in range(1 + _AGR_COORD_ZOOMS):
+        best_g, best_D = evaluate(trials, best_g, best_D)
+        if r == _AGR_COORD_ZOOMS:
+            break
+        below = torch.where(nodes < best_g, nodes, ninf).max()
+        above = torch.where(nodes > best_g, nodes, -ninf).min()
+        lo = torch.where(torch.isfinite(below), below, best_g)
+        hi = torch.where(torch.isfinite(above), above, best_g)
+        trials = (lo + (hi - lo) * frac / (_AGR_COORD_POINTS + 1)).float().double()
+        nodes = torch.cat([lo[None], trials, hi[None]])
+    return torch.where(ok, best_g, zero).to(a.dtype)
+
+
+def agr_coord(
+    X: torch.Tensor,
+    f: int,
+    agr: str = "trimmed-mean",
+    perturbation: str = "std",
+) -> torch.Tensor:
+    """Attack vector m = mu + gamma p against ``agr`` in "trimmed-mean" |
+    "median" run on the n honest rows of X plus f copies of m. On device: the
+    statistics pass, three objective passes, one addcmul — no host sync,
+    capturable into a hipGraph. CPU tensors take the functional path."""
+    _perturb_code(perturbation)
+    F.agr_coord_check(X.shape[0], int(f), agr)
+    if not _attack_device(X):
+        return F.agr_coord(X, int(f), agr, perturbation)
+    mu, p, a, _, c = attack_stats(X, perturbation)
+    gamma = agr_coord_gamma(X, mu, p, a, c, f, agr)
+    return torch.addcmul(mu, gamma.to(mu.dtype), p).to(X.dtype)
+
+
 # -- remaining ops: torch composition on either device ----------------------
 
 

@@ -938,3 +938,152 @@ def agr_tailored(
     mu, p = attack_perturbation(honest, perturbation)
     gamma = agr_tailored_gamma(honest, f, agr, q, perturbation)
     return (mu + gamma * p).to(honest.dtype)
+
+
+# Tailored attacks on the coordinate-wise rules (Shejwalkar & Houmansadr,
+# NDSS 2021, section IV-B): against the trimmed mean and the median the
+# adversary sends f copies of m = mu + gamma * p with the gamma that moves the
+# rule's output farthest from the honest mean, D(gamma) = ||mu - A(gamma)||^2.
+# D is bounded and not monotone, so gamma comes from a fixed maximisation
+# schedule, not a boundary search. The oracle's own text: the explicit
+# (n + f, d) attacked matrix, a sort, the rule read off the sorted rows. The
+# device path (hip/dispatch.py) sorts the honest rows once and never builds
+# the attacked matrix.
+
+AGR_COORD_RULES = ("trimmed-mean", "median")
+
+# The schedule, shared in words with hip/dispatch.py: round 0 tries gamma = 0
+# and gamma0 2^k, k = -15 .. 15; each of the two zoom rounds places 32 equally
+# spaced points strictly inside (lo, hi), the evaluated points next below and
+# next above the incumbent (the incumbent itself where there is none). The
+# largest D wins, equal D goes to the smaller gamma, a D that is not finite
+# never wins. Every trial gamma is an f32 value (what the device kernel
+# takes), worked out in f64 and rounded.
+_COORD_GEO = tuple(range(-15, 16))
+_COORD_POINTS = 32
+_COORD_ZOOMS = 2
+
+
+def agr_coord_check(n: int, f: int, agr: str) -> None:
+    if agr not in AGR_COORD_RULES:
+        raise ValueError(f"agr must be one of {AGR_COORD_RULES}, got {agr!r}")
+    if f < 1:
+        raise ValueError(f"a tailored attack needs f >= 1, got f={f}")
+    if agr == "trimmed-mean" and f >= n:
+        raise ValueError(
+            f"the trimmed mean of n + f rows drops 2f: need f < n, got n={n}, f={f}"
+        )
+
+
+def _coord_rule(A: torch.Tensor, f: int, agr: str) -> torch.Tensor:
+    """The rule on the rows of A in A's own dtype: the text of ``median`` /
+    ``trimmed_mean`` above without their casts to f32."""
+    N = A.shape[0]
+    s, _ = torch.sort(A, dim=0)
+    if agr == "median":
+        if N % 2 == 1:
+            return s[N // 2]
+        return (s[N // 2 - 1] + s[N // 2]) * 0.5
+    return s[f : N - f].mean(dim=0)
+
+
+def agr_coord_objective(
+    honest: torch.Tensor,
+    gamma: float,
+    f: int,
+    agr: str,
+    perturbation: str = "std",
+    *,
+    mu: Optional[torch.Tensor] = None,
+    p: Optional[torch.Tensor] = None,
+    dtype: torch.dtype = torch.float64,
+) -> float:
+    """D(gamma) = sum_j (mu_j - A_j)^2, A the rule's output on the honest rows
+    followed by f copies of mu + gamma p. ``mu`` and ``p`` default to
+    ``attack_perturbation``; given, they are used as they are (mu need not be
+    the column mean). ``dtype`` is the arithmetic of every step up to mu - A;
+    the squares are summed in f64 either way."""
+    agr_coord_check(honest.shape[0], int(f), agr)
+    if mu is None or p is None:
+        mu0, p0 = attack_perturbation(honest, perturbation)
+        mu = mu0 if mu is None else mu
+        p = p0 if p is None else p
+    mu, p = mu.to(dtype), p.to(dtype)
+    m = mu + torch.tensor(float(gamma), dtype=dtype) * p
+    A = torch.cat([honest.to(dtype), m[None, :].expand(int(f), -1)], dim=0)
+    diff = (mu - _coord_rule(A, int(f), agr)).double()
+    return float((diff * diff).sum())
+
+
+def _f32(x: float) -> float:
+    return float(torch.tensor(x, dtype=torch.float64).float())
+
+
+def _coord_better(D: float, g: float, best_D: float, best_g: float) -> bool:
+    if not math.isfinite(D):
+        return False
+    return D > best_D or (D == best_D and g < best_g)
+
+
+def agr_coord_gamma(
+    honest: torch.Tensor,
+    f: int,
+    agr: str,
+    perturbation: str = "std",
+    *,
+    gamma0: Optional[float] = None,
+    mu: Optional[torch.Tensor] = None,
+    p: Optional[torch.Tensor] = None,
+) -> float:
+    """The gamma of the schedule above. The anchor gamma0 defaults to the
+    Min-Sum value sqrt(max_i a_i / c), and gamma is then 0 when c = 0 or a
+    statistic is not finite; a given ``gamma0`` is taken as it is (c is not
+    looked at) and gives 0 when it is not finite. gamma is 0 when no trial's
+    D is finite."""
+    agr_coord_check(honest.shape[0], int(f), agr)
+    mu0, p0 = attack_perturbation(honest, perturbation)
+    mu = mu0 if mu is None else mu
+    p = p0 if p is None else p
+    if gamma0 is None:
+        diff = mu.double()[None, :] - honest.double()
+        a_max = float((diff * diff).sum(dim=1).max())
+        c = float((p.double() * p.double()).sum())
+        if not (c > 0.0 and math.isfinite(c)):
+            return 0.0
+        gamma0 = math.sqrt(a_max / c) if a_max >= 0.0 else float("nan")
+    gamma0 = _f32(float(gamma0))
+    if not math.isfinite(gamma0):
+        return 0.0
+
+    def D(g):
+        return agr_coord_objective(honest, g, f, agr, perturbation, mu=mu, p=p)
+
+    best_g, best_D = 0.0, -math.inf
+    trials = [0.0] + [_f32(gamma0 * 2.0**k) for k in _COORD_GEO]
+    nodes = trials  # the points that can bound the next round's interval
+    for r in range(1 + _COORD_ZOOMS):
+        for g in trials:
+            Dg = D(g)
+            if _coord_better(Dg, g, best_D, best_g):
+                best_g, best_D = g, Dg
+        if r == _COORD_ZOOMS:
+            break
+        lo = max([x for x in nodes if x < best_g], default=best_g)
+        hi = min([x for x in nodes if x > best_g], default=best_g)
+        trials = [
+            _f32(lo + (hi - lo) * j / (_COORD_POINTS + 1))
+            for j in range(1, _COORD_POINTS + 1)
+        ]
+        nodes = [lo] + trials + [hi]
+    return best_g
+
+
+def agr_coord(
+    honest: torch.Tensor,
+    f: int,
+    agr: str = "trimmed-mean",
+    perturbation: str = "std",
+) -> torch.Tensor:
+    mu, p = attack_perturbation(honest, perturbation)
+    gamma = agr_coord_gamma(honest, f, agr, perturbation)
+    return (mu + gamma * p).to(honest.dtype)
