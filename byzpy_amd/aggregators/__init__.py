@@ -21,6 +21,7 @@ from byzpy_amd.aggregators.norm_wise import (
     CenteredClipping,
     ComparativeGradientElimination,
 )
+from byzpy_amd.aggregators.pre_aggregated import PreAggregated
 
 __all__ = [
     "Aggregator",
@@ -40,4 +41,5 @@ __all__ = [
     "CenteredClipping",
     "ComparativeGradientElimination",
     "CAF",
+    "PreAggregated",
 ]

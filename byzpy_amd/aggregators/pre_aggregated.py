@@ -1,0 +1,46 @@
+"""A pre-aggregator and an aggregator as one aggregator.
+
+The literature pairs a mixing pre-aggregator with a coordinate-wise rule:
+NNM then trimmed mean (Allouah et al. 2023), Bucketing then median
+(Karimireddy et al. 2022). Both pre-aggregators are row maps Y = W X with a
+tiny 0/1 membership matrix W over its row counts, so on the device the pair
+needs no mixed matrix Y at all: ``colsel(X, mode, f, mix=W)`` (K18,
+colsel_mix.hip) rebuilds every mixed column in registers and runs the rule's
+selection network on it.
+"""
+from __future__ import annotations
+
+import torch
+
+from byzpy_amd.aggregators.base import Aggregator
+from byzpy_amd.aggregators.coordinate_wise import (
+    CoordinateWiseMedian,
+    CoordinateWiseTrimmedMean,
+)
+from byzpy_amd.hip import dispatch as D
+
+
+class PreAggregated(Aggregator):
+    """``aggregator`` applied to the output of ``pre_aggregator``.
+
+    A pre-aggregator with a ``membership(X)`` method (NearestNeighborMixing,
+    Bucketing) in front of CoordinateWiseMedian or CoordinateWiseTrimmedMean
+    takes the fused device route where ``D.mixed_colsel_fused_ok(X)``;
+    everything else is
+    ``aggregator._aggregate(pre_aggregator._pre_aggregate(X))``."""
+
+    name = "pre-aggregated"
+    supports_subtasks = False
+
+    def __init__(self, pre_aggregator, aggregator: Aggregator) -> None:
+        self.pre_aggregator = pre_aggregator
+        self.aggregator = aggregator
+
+    def _aggregate(self, X: torch.Tensor) -> torch.Tensor:
+        pre, agg = self.pre_aggregator, self.aggregator
+        if hasattr(pre, "membership") and D.mixed_colsel_fused_ok(X):
+            if type(agg) is CoordinateWiseMedian:
+                return D.mixed_median(X, pre.membership(X))
+            if type(agg) is CoordinateWiseTrimmedMean:
+                return D.mixed_trimmed_mean(X, pre.membership(X), agg.f)
+        return agg._aggregate(pre._pre_aggregate(X))

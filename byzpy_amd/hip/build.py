@@ -19,9 +19,16 @@ CSRC = PKG_DIR / "hip" / "csrc"
 OUT_SO = PKG_DIR / "_hip_ops.so"
 BUILD_DIR = PKG_DIR.parent / "build" / "hip"
 
-SOURCES = ["colsel.hip", "rsel.hip", "rowops.hip", "gram.hip", "krumsel.hip",
-           "subsets.hip", "attacks.hip", "mda_host.cpp", "bind.cpp"]
-HEADERS = ["common.h", "launchers.h", "mda_host.h", "oem_sort.h", "selnet.h"]
+SOURCES = ["colsel.hip", "colsel_mix.hip", "rsel.hip", "rowops.hip", "gram.hip",
+           "krumsel.hip", "subsets.hip", "attacks.hip", "mda_host.cpp", "bind.cpp"]
+HEADERS = ["common.h", "launchers.h", "mda_host.h", "oem_sort.h", "selnet.h",
+           "colsel_shared.h"]
+
+# Per-file flags. colsel_mix.hip keeps its f32 scaling and summing on the
+# one-value-per-lane VALU forms: built without v_pk_add/mul/fma_f32.
+EXTRA_FLAGS = {
+    "colsel_mix.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
 
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
@@ -77,7 +84,7 @@ def build(force: bool = False, verbose: bool = True) -> Path:
 
     def compile_one(src: str) -> str:
         obj = str(BUILD_DIR / (Path(src).stem + ".o"))
-        cmd = common + ["-c", str(CSRC / src), "-o", obj]
+        cmd = common + EXTRA_FLAGS.get(src, []) + ["-c", str(CSRC / src), "-o", obj]
         if src.endswith(".hip"):
             cmd.insert(1, "-xhip")
         if verbose:

@@ -257,6 +257,45 @@ torch::Tensor colsel_objective(torch::Tensor X, int64_t mode, int64_t f,
   return out;
 }
 
+// colsel(X, mode, f, mix=M): the column median (mode 0) or f-trimmed mean
+// (mode 1) of the mixed rows y_i = mean of the rows k of X with M[i][k] != 0
+// (colsel_mix.hip, K18). X is bf16 (n, d), M a uint8 (m, n) device matrix
+// with no empty row, n and m <= 64. Returns the bf16 (d,) result; the
+// (m, d) mixed matrix is never written. No host sync.
+torch::Tensor colsel_mix(torch::Tensor X, int64_t mode, int64_t f,
+                         torch::Tensor mix) {
+  TORCH_CHECK(X.is_cuda() && mix.is_cuda(), "expected device tensors");
+  TORCH_CHECK(X.dim() == 2 && X.is_contiguous() &&
+                  X.scalar_type() == torch::kBFloat16,
+              "colsel(mix=): expected a bf16 contiguous (n, d) matrix");
+  TORCH_CHECK(mix.scalar_type() == torch::kUInt8 && mix.dim() == 2 &&
+                  mix.is_contiguous(),
+              "mix: expected a uint8 contiguous (m, n) matrix");
+  TORCH_CHECK(mix.device() == X.device(), "mix: expected X's device");
+  const int64_t n = X.size(0), m = mix.size(0);
+  const long d = (long)X.size(1);
+  TORCH_CHECK(mix.size(1) == n, "mix: expected (m, ", n, "), got (", m, ", ",
+              mix.size(1), ")");
+  TORCH_CHECK(n >= 1 && n <= COLSEL_MIX_MAX && m >= 1 && m <= COLSEL_MIX_MAX,
+              "colsel(mix=) supports 1 <= n, m <= ", COLSEL_MIX_MAX,
+              ", got n=", n, ", m=", m);
+  TORCH_CHECK(mode == 0 || mode == 1, "colsel(mix=): expected mode 0 (median) ",
+              "or 1 (trimmed mean), got ", mode);
+  TORCH_CHECK(f >= 0 && (mode == 0 || 2 * f < m),
+              "colsel(mix=) needs f >= 0, and 2f < m for the trimmed mean, ",
+              "got m=", m, ", f=", f);
+  auto out = torch::empty({d}, X.options());
+  if (d == 0) return out;
+  auto scratch = torch::empty({COLSEL_MIX_SCRATCH_WORDS},
+                              X.options().dtype(torch::kInt64));
+  launch_colsel_mix_bf16(
+      ptr<__hip_bfloat16>(X), mix.data_ptr<uint8_t>(),
+      reinterpret_cast<unsigned long long*>(scratch.data_ptr<int64_t>()),
+      ptr<__hip_bfloat16>(out), (int)n, (int)m, d, (int)mode, (int)f,
+      cur_stream());
+  return out;
+}
+
 torch::Tensor row_sqnorms(torch::Tensor X) {
   check_matrix(X);
   const int n = (int)X.size(0);
@@ -840,6 +879,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "coordinate-wise tailored attack objective: f64 D per trial gamma",
         py::arg("X"), py::arg("mode"), py::arg("f"), py::kw_only(),
         py::arg("mu"), py::arg("p"), py::arg("gammas"));
+  m.def("colsel", &colsel_mix,
+        "median / trimmed mean of the rows mixed by a membership matrix (K18)",
+        py::arg("X"), py::arg("mode"), py::arg("f"), py::kw_only(),
+        py::arg("mix"));
   m.def("row_sqnorms", &row_sqnorms);
   m.def("row_center_sqdists", &row_center_sqdists);
   m.def("row_scale", &row_scale);

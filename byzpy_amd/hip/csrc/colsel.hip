@@ -22,30 +22,11 @@
 //
 // Loads are coalesced: adjacent lanes read adjacent columns, so each
 // row-iteration is one 256 B (f32) / 128 B (bf16) wave transaction.
-#include "common.h"
+#include "colsel_shared.h"
 #include "launchers.h"
 #include "selnet.h"
-#include <type_traits>
 
 namespace {
-
-// +inf (not a big-finite sentinel): adversarial rows can BE +inf
-// (InfAttack) and pads must never sort below a real value — with inf pads
-// a pad/value tie still yields the mathematically-correct inf statistics.
-#define PAD __builtin_huge_valf()
-
-// Copy a wave-uniform int into a VGPR. Unrolled predicates like
-// `i == pos` / `i >= n` (i compile-time, pos/n uniform) otherwise become
-// batched s_cmp/s_cselect_b64 SGPR mask pairs — ~64 live masks spill
-// through v_writelane/readlane and dominate the kernel. Against a VGPR
-// operand they lower to v_cmp/v_cndmask instead (2 VALU each, no spills).
-DEV int vecify(int x) {
-  int r;
-  asm("v_mov_b32_e32 %0, %1" : "=v"(r) : "s"(x));
-  return r;
-}
-
-enum Mode { MEDIAN = 0, TRIMMED = 1, MEAMED = 2 };
 
 // ---------------------------------------------------------------------------
 // Row-indexed variants (template <bool ROWS>): the statistic runs over the
@@ -70,8 +51,6 @@ enum Mode { MEDIAN = 0, TRIMMED = 1, MEAMED = 2 };
 // keep whole waves active (see wave_active) and clamp/predicate the tail
 // lanes instead of dropping them.
 // ---------------------------------------------------------------------------
-
-typedef unsigned int u32;
 
 struct RowOffsets { u32 lo, hi; };
 
@@ -111,12 +90,6 @@ DEV bool wave_active(long unit, long nunits) {
 // ---------------------------------------------------------------------------
 // register variant, n <= P, P in {8, 16, 32, 64}
 // ---------------------------------------------------------------------------
-
-// min/max policy of the selnet.h networks on f32 registers
-struct F32MinMax {
-  static DEV float mn(float a, float b) { return fminf(a, b); }
-  static DEV float mx(float a, float b) { return fmaxf(a, b); }
-};
 
 // key-value bitonic sort (sort key ascending, carry val along): it swaps on
 // a comparison, so it is not a min/max network and stays here
@@ -717,14 +690,6 @@ constexpr int MG_EVENTS = 4 * (1 + MG_TILES);
 static_assert(3 * MG_STEP + MG_LEAD + (MG_TILES - 1) * MG_GAP <= MG_NET_OPS - 2,
               "the last MFMA must be due before the network's last group");
 
-// Orders this wave's LDS accesses before the fence against those after it,
-// for the compiler only: the LDS serves one wave's operations in order.
-DEV void mg_wave_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // FULL: n == 64 (no pad slots, no row clamp), chosen by the launcher so
 // that each instantiation has ONE load walk: with both in one kernel the
 // prefetched words reach the loop's end through 33 register copies.
@@ -793,7 +758,7 @@ median_gram_bf16_kernel(const unsigned short* __restrict__ X,
   auto strip = [&](u32 (&v)[P], u32 (&r)[P]) __attribute__((always_inline)) {
     const long pair = u * 64 + lane;
     const bool valid = pair < npairs;
-    mg_wave_fence();  // the last strip's fragment reads stay above the stores
+    wave_lds_fence();  // the last strip's fragment reads stay above the stores
     // raw words into the slab
     if (FULL && (u + 1) * 64 <= npairs) {
 #pragma unroll
@@ -836,7 +801,7 @@ median_gram_bf16_kernel(const unsigned short* __restrict__ X,
     // unconditional: behind a branch the 64 words come back through copies
     // at the loop's end
     load_strip(r, u_next, u);
-    mg_wave_fence();  // the slab is complete for this wave's own reads
+    wave_lds_fence();  // the slab is complete for this wave's own reads
 
     // Gram of the slab inside the selection network. Event 11 * s + m is
     // k-step s's fragment reads (m == 0: one per 16-row block) or its MFMA
@@ -921,7 +886,7 @@ median_gram_bf16_kernel(const unsigned short* __restrict__ X,
   const int ln =
       __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
   const int er = ln & 15, eq = ln >> 4;
-  mg_wave_fence();
+  wave_lds_fence();
   float* const part = reinterpret_cast<float*>(slab) + ln;
 #pragma unroll
   for (int e = 0; e < MG_TILES; ++e)
@@ -1278,24 +1243,6 @@ __global__ void coord_objective_finish(const double* __restrict__ part,
   double s = 0.0;
   for (int b = 0; b < nblocks; ++b) s += part[(long)b * COORD_T + t];
   out[t] = s;
-}
-
-// Turns the runtime mode / row count into the kernels' template arguments:
-// fn receives std::integral_constant<int, MODE> / <int, P>.
-template <typename F>
-inline void by_mode(int mode, F&& fn) {
-  if (mode == MEDIAN) fn(std::integral_constant<int, MEDIAN>{});
-  else if (mode == TRIMMED) fn(std::integral_constant<int, TRIMMED>{});
-  else fn(std::integral_constant<int, MEAMED>{});
-}
-
-// padded register width of the n <= 64 kernels
-template <typename F>
-inline void by_reg_width(int n, F&& fn) {
-  if (n <= 8) fn(std::integral_constant<int, 8>{});
-  else if (n <= 16) fn(std::integral_constant<int, 16>{});
-  else if (n <= 32) fn(std::integral_constant<int, 32>{});
-  else fn(std::integral_constant<int, 64>{});
 }
 
 // plain (rows == nullptr) or row-indexed kernel variant:

@@ -52,6 +52,21 @@ void launch_median_gram_bf16(const __hip_bfloat16* X, __hip_bfloat16* med,
                              float* G, unsigned long long* ticket, int n,
                              long d, hipStream_t stream);
 
+// colsel_mix.hip (K18): column median (mode 0) / f-trimmed mean (mode 1) of
+// the m mixed rows y_i = mean of the rows k of X with mix[i][k] != 0, with
+// no (m, d) intermediate. bf16 X (n, d), mix (m, n) bytes on the device,
+// 1 <= n, m <= COLSEL_MIX_MAX, d >= 1, 2f < m in mode 1. y_i is the f32 sum
+// of exactly its members over their count: rows that are no members never
+// touch it, whatever they hold; a NaN y_i ranks last, as in torch.sort.
+// `scratch` is COLSEL_MIX_SCRATCH_WORDS 64-bit words, written by the first
+// of the two launches (bit rows and counts of mix). No host sync.
+constexpr int COLSEL_MIX_MAX = 64;
+constexpr int COLSEL_MIX_SCRATCH_WORDS = 97;
+void launch_colsel_mix_bf16(const __hip_bfloat16* X, const unsigned char* mix,
+                            unsigned long long* scratch, __hip_bfloat16* out,
+                            int n, int m, long d, int mode, int f,
+                            hipStream_t stream);
+
 // colsel.hip: objective of the coordinate-wise tailored attack. For each of
 // the ntrials values of gammas, out[t] = sum_j (mu_j - A_j)^2 in f64, A_j the
 // median (mode 0) or f-trimmed mean (mode 1) of column j's n honest values

@@ -833,6 +833,65 @@ def nnm(X: torch.Tensor, f: int) -> torch.Tensor:
     return F.nnm(X, f)
 
 
+# -- mixing pre-aggregator + coordinate-wise rule (K18) ----------------------
+
+# NNM and Bucketing are row maps Y = W X, W an (m, n) 0/1 membership matrix
+# over its row counts. ``colsel(X, mode, f, mix=)`` (colsel_mix.hip) takes
+# the median / trimmed mean of W X column by column with the matrix pipe and
+# never writes the (m, d) matrix Y that the composition stores (rounded to
+# bf16) and reads back.
+MIXED_COLSEL_MAX = 64
+
+# Column count from which the fused kernel is the default route. Measured on
+# MI355X at n = 33 and n = 64, d = 64K ... 16M, NNM -> trimmed mean, the mix
+# + select step alone with the membership given
+# (benchmarks/RESULTS_MI355X_mixed.md, "d sweep"): the fused call took
+# 0.06-0.52 of the composition's time at EVERY size, 64K included (11.9 vs
+# 23.1 us at 33 x 65,536, 15.6 vs 36.7 us at 64 x 65,536), with a run-to-run
+# spread under 1 % on either side. 65,536 is the smallest size measured;
+# below it the composition stays.
+MIXED_COLSEL_FUSED_MIN_D = 65_536
+
+# BYZPY_MIXED_COLSEL=split forces the composition, =fused the kernel
+# wherever it applies (A/B runs)
+_MIXED_COLSEL_ENV = "BYZPY_MIXED_COLSEL"
+
+
+def mixed_colsel_fused_ok(X: torch.Tensor) -> bool:
+    """Whether a mixed statistic of X's rows takes the fused kernel: bf16 on
+    the device, n <= 64 (so m <= 64 for NNM and Bucketing), d past the
+    routing threshold."""
+    n, d = X.shape
+    if not (_gpu(X) and X.dtype == torch.bfloat16 and 1 <= n <= MIXED_COLSEL_MAX and d >= 1):
+        return False
+    env = os.environ.get(_MIXED_COLSEL_ENV, "")
+    if env == "split":
+        return False
+    if env == "fused":
+        return True
+    return d >= MIXED_COLSEL_FUSED_MIN_D
+
+
+def _mixed_colsel(X: torch.Tensor, mix: torch.Tensor, mode: int, f: int):
+    """Median / trimmed mean over the rows of Y = (mix @ X) / mix.sum(1):
+    the fused kernel where mixed_colsel_fused_ok, else Y in f32, rounded to
+    X's dtype as the pre-aggregators round theirs, and the plain rule."""
+    if mixed_colsel_fused_ok(X) and mix.shape[0] <= MIXED_COLSEL_MAX:
+        mix8 = mix.to(device=X.device, dtype=torch.uint8).contiguous()
+        return _hip.require().colsel(X.contiguous(), mode, int(f), mix=mix8)
+    W = mix.to(device=X.device, dtype=torch.float32)
+    Y = ((W @ X.float()) / W.sum(dim=1, keepdim=True)).to(X.dtype)
+    return median(Y) if mode == _COLSEL_MEDIAN else trimmed_mean(Y, f)
+
+
+def mixed_median(X: torch.Tensor, mix: torch.Tensor) -> torch.Tensor:
+    return _mixed_colsel(X, mix, _COLSEL_MEDIAN, 0)
+
+
+def mixed_trimmed_mean(X: torch.Tensor, mix: torch.Tensor, f: int) -> torch.Tensor:
+    return _mixed_colsel(X, mix, _COLSEL_TRIMMED, f)
+
+
 # -- attack math (K14) ------------------------------------------------------
 
 

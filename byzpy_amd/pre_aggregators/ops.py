@@ -91,6 +91,17 @@ class Bucketing(PreAggregator):
     def _pre_aggregate(self, X: torch.Tensor) -> torch.Tensor:
         return D.bucketing(X, self.bucket_size, self._draw_perm(X.shape[0]))
 
+    def membership(self, X: torch.Tensor) -> torch.Tensor:
+        """The (ceil(n / s), n) 0/1 matrix of the bucketing of X's rows, on
+        X's device: row b marks the rows of bucket b of one drawn permutation
+        (the last bucket may be ragged). ``_pre_aggregate`` returns the row
+        means this matrix describes."""
+        n = X.shape[0]
+        perm = torch.as_tensor(self._draw_perm(n), dtype=torch.long)
+        mix = torch.zeros((-(-n // self.bucket_size), n), dtype=torch.uint8)
+        mix[torch.arange(n) // self.bucket_size, perm] = 1
+        return mix.to(X.device)
+
     def create_subtasks(self, ctx: OpContext, **inputs: Any) -> Sequence[SubTask]:
         vectors = inputs[self.input_key]
         ref, X, like, handles = self._matrix_ref(ctx, vectors)
@@ -129,6 +140,15 @@ class NearestNeighborMixing(PreAggregator):
 
     def _pre_aggregate(self, X: torch.Tensor) -> torch.Tensor:
         return D.nnm(X, self.f)
+
+    def membership(self, X: torch.Tensor) -> torch.Tensor:
+        """The (n, n) 0/1 matrix of the mixing, on X's device: row i marks
+        the n - f nearest rows of row i (itself included), the indices
+        ``_pre_aggregate`` averages."""
+        n = X.shape[0]
+        idx = D.nearest_rows_from_gram(D.gram(X), n - self.f)
+        mix = torch.zeros((n, n), dtype=torch.uint8, device=X.device)
+        return mix.scatter_(1, idx, 1)
 
     def create_subtasks(self, ctx: OpContext, **inputs: Any) -> Sequence[SubTask]:
         vectors = inputs[self.input_key]
