@@ -18,7 +18,12 @@ from byzpy_amd.storage.shared_store import (
     cleanup_tensor,
     register_tensor,
 )
-from byzpy_amd.utils.flatten import LikeTemplate, stack_gradients, to_like
+from byzpy_amd.utils.flatten import (
+    LikeTemplate,
+    rows_in_place,
+    stack_gradients,
+    to_like,
+)
 
 
 def build_matrix_ref(
@@ -50,12 +55,22 @@ class Aggregator(Operator):
 
     # -- public API --------------------------------------------------------
     def aggregate(self, gradients: Any) -> Any:
+        if self._aggregate_rows is not None:
+            rows = rows_in_place(gradients)
+            if rows is not None:
+                out = self._aggregate_rows(rows)
+                return to_like(out.reshape(-1), LikeTemplate(gradients[0]))
         X, like = stack_gradients(gradients)
         out = self._aggregate(X)
         return to_like(out.reshape(-1), like)
 
     def _aggregate(self, X: torch.Tensor) -> torch.Tensor:
         raise NotImplementedError
+
+    # Optional hook: the aggregate of a list of n <= 64 flat device rows read
+    # where they are (utils.flatten.rows_in_place), with no stacked (n, d)
+    # matrix. Rules that have no such path leave it None.
+    _aggregate_rows = None
 
     # -- Operator ----------------------------------------------------------
     def compute(self, ctx: OpContext, **inputs: Any) -> Any:

@@ -74,6 +74,9 @@ class CoordinateWiseMedian(_FeatureChunkedAggregator):
     def _aggregate(self, X: torch.Tensor) -> torch.Tensor:
         return D.median(X)
 
+    def _aggregate_rows(self, rows: List[torch.Tensor]) -> torch.Tensor:
+        return D.median(rows)
+
     def _chunk_fn(self):
         return SF.median_chunk
 
@@ -93,6 +96,9 @@ class CoordinateWiseTrimmedMean(_FeatureChunkedAggregator):
 
     def _aggregate(self, X: torch.Tensor) -> torch.Tensor:
         return D.trimmed_mean(X, self.f)
+
+    def _aggregate_rows(self, rows: List[torch.Tensor]) -> torch.Tensor:
+        return D.trimmed_mean(rows, self.f)
 
     def _chunk_fn(self):
         return SF.trimmed_mean_chunk
@@ -115,6 +121,9 @@ class MeanOfMedians(_FeatureChunkedAggregator):
 
     def _aggregate(self, X: torch.Tensor) -> torch.Tensor:
         return D.mean_of_medians(X, self.f)
+
+    def _aggregate_rows(self, rows: List[torch.Tensor]) -> torch.Tensor:
+        return D.mean_of_medians(rows, self.f)
 
     def _chunk_fn(self):
         return SF.meamed_chunk

@@ -41,6 +41,9 @@ class MultiKrum(Aggregator):
     def _aggregate(self, X: torch.Tensor) -> torch.Tensor:
         return D.multi_krum(X, self.f, self.q)
 
+    def _aggregate_rows(self, rows: List[torch.Tensor]) -> torch.Tensor:
+        return D.multi_krum(rows, self.f, self.q)
+
     def create_subtasks(self, ctx: OpContext, **inputs: Any) -> Sequence[SubTask]:
         gradients = inputs[self.input_key]
         ref, X, like, handles = self._matrix_ref(ctx, gradients)
@@ -74,6 +77,9 @@ class Krum(MultiKrum):
 
     def _aggregate(self, X: torch.Tensor) -> torch.Tensor:
         return D.krum(X, self.f)
+
+    def _aggregate_rows(self, rows: List[torch.Tensor]) -> torch.Tensor:
+        return D.krum(rows, self.f)
 
     def reduce_subtasks(self, ctx: OpContext, results: List[Any], **inputs: Any) -> Any:
         X, like, handles = ctx.metadata.pop("_op_pending")

@@ -480,6 +480,83 @@ std::vector<torch::Tensor> gram_sampled(torch::Tensor X, torch::Tensor cols) {
   return {Gc, bad};
 }
 
+// -- row-pointer layout (K19) ------------------------------------------------
+// colsel / gram / mean_rows over a LIST of n <= 64 1-D device tensors, read
+// in place through a by-value pointer table: no stacked (n, d) copy.
+
+// Validates the list before anything touches the device; returns the table
+// (slots past n repeat the last row).
+RowPtrTable check_row_list(const std::vector<torch::Tensor>& rows,
+                           const char* op) {
+  const int64_t n = (int64_t)rows.size();
+  TORCH_CHECK(n >= 1 && n <= ROWPTR_MAX_N, op, "(rows) supports 1 <= ",
+              "len(rows) <= ", ROWPTR_MAX_N, ", got ", n);
+  const torch::Tensor& r0 = rows[0];
+  RowPtrTable tbl;
+  for (int64_t i = 0; i < n; ++i) {
+    const torch::Tensor& r = rows[i];
+    TORCH_CHECK(r.is_cuda(), op, "(rows): expected device tensors");
+    TORCH_CHECK(r.dim() == 1 && r.is_contiguous(), op,
+                "(rows): expected 1-D contiguous tensors");
+    TORCH_CHECK(r.scalar_type() == torch::kFloat32 ||
+                    r.scalar_type() == torch::kBFloat16,
+                op, "(rows): expected f32 or bf16");
+    TORCH_CHECK(r.scalar_type() == r0.scalar_type() &&
+                    r.numel() == r0.numel() && r.device() == r0.device(),
+                op, "(rows): every row must share row 0's dtype, length and ",
+                "device");
+    tbl.p[i] = r.data_ptr();
+  }
+  TORCH_CHECK(r0.numel() >= 1, op, "(rows): expected at least one column");
+  for (int64_t i = n; i < ROWPTR_MAX_N; ++i) tbl.p[i] = tbl.p[n - 1];
+  return tbl;
+}
+
+torch::Tensor colsel_rowlist(std::vector<torch::Tensor> rows, int64_t mode,
+                             int64_t f) {
+  const RowPtrTable tbl = check_row_list(rows, "colsel");
+  const int n = (int)rows.size();
+  TORCH_CHECK(mode >= 0 && mode <= 2, "colsel(rows): expected mode 0, 1 or 2");
+  check_colsel_f(mode, f, n);
+  const long d = (long)rows[0].numel();
+  auto out = torch::empty({d}, rows[0].options());
+  by_dtype(rows[0], [&](auto tag) {
+    using T = TAG_T(tag);
+    launch_colsel_rowptrs<T>(tbl, ptr<T>(out), n, d, (int)mode, (int)f,
+                             cur_stream());
+  });
+  return out;
+}
+
+torch::Tensor gram_rowlist(std::vector<torch::Tensor> rows) {
+  const RowPtrTable tbl = check_row_list(rows, "gram");
+  const int n = (int)rows.size();
+  const long d = (long)rows[0].numel();
+  auto G = torch::zeros({n, n}, f32_like(rows[0]));
+  by_dtype(rows[0], [&](auto tag) {
+    using T = TAG_T(tag);
+    launch_gram_rowptrs<T>(tbl, f32(G), n, d, cur_stream());
+  });
+  return G;
+}
+
+torch::Tensor mean_rows_rowlist(std::vector<torch::Tensor> rows,
+                                torch::Tensor idx) {
+  const RowPtrTable tbl = check_row_list(rows, "mean_rows");
+  check_i32(idx, 1, "idx");
+  TORCH_CHECK(idx.numel() >= 1 && idx.numel() <= INT_MAX,
+              "idx: expected at least one row");
+  TORCH_CHECK(idx.device() == rows[0].device(), "idx: expected the rows' device");
+  const long d = (long)rows[0].numel();
+  auto out = torch::empty({d}, rows[0].options());
+  by_dtype(rows[0], [&](auto tag) {
+    using T = TAG_T(tag);
+    launch_mean_rows_rowptrs<T>(tbl, (int)rows.size(), i32(idx),
+                                (int)idx.numel(), ptr<T>(out), d, cur_stream());
+  });
+  return out;
+}
+
 // Fused Krum selection: Gram -> q winner indices (one kernel, replaces
 // the D2-build + two topk torch chains whose launch overhead caps the
 // d-sharded multi-GPU scaling).
@@ -883,6 +960,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "median / trimmed mean of the rows mixed by a membership matrix (K18)",
         py::arg("X"), py::arg("mode"), py::arg("f"), py::kw_only(),
         py::arg("mix"));
+  m.def("colsel", &colsel_rowlist,
+        "the same statistics over a list of n <= 64 1-D device rows (K19)",
+        py::arg("rows"), py::arg("mode"), py::arg("f"));
   m.def("row_sqnorms", &row_sqnorms);
   m.def("row_center_sqdists", &row_center_sqdists);
   m.def("row_scale", &row_scale);
@@ -894,12 +974,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "weighted mean of rows idx[:count], one f32 weight per row of X (K16)",
         py::arg("X"), py::arg("idx"), py::kw_only(), py::arg("count"),
         py::arg("weights"));
+  m.def("mean_rows", &mean_rows_rowlist,
+        "mean of rows[idx[i]] over a list of n <= 64 1-D device rows (K19)",
+        py::arg("rows"), py::arg("idx"));
   m.def("group_mean_rows", &group_mean_rows);
   m.def("bucket_mean", &bucket_mean);
   m.def("gram", &gram);
   m.def("gram", &gram_sampled,
         "sampled centred Grams of DnC (K15): (Gc, bad)", py::arg("X"),
         py::kw_only(), py::arg("cols"));
+  m.def("gram", &gram_rowlist,
+        "Gram of a list of n <= 64 1-D device rows, read in place (K19)",
+        py::arg("rows"));
   m.def("krum_select", &krum_select, py::arg("G"), py::arg("f"), py::arg("q"),
         py::arg("iterative") = false);
   m.def("krum_select", &agr_search,

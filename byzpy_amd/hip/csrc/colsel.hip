@@ -54,6 +54,22 @@ namespace {
 
 struct RowOffsets { u32 lo, hi; };
 
+// what ROWS means to the register kernels. ROWS_PTRS (K19): the rows are
+// separate vectors named by a RowPtrTable passed by value as the kernel's
+// last argument (a parameter pack that is empty otherwise, so the other
+// instantiations keep their signature), X is row 0, and the staged offsets
+// are the pointer differences from it (unsigned wrap is fine: at_row adds
+// them back to a pointer into row 0).
+enum RowsKind { ROWS_NONE = 0, ROWS_INDEX = 1, ROWS_PTRS = 2 };
+
+DEV RowOffsets stage_ptr_offsets(const RowPtrTable& tbl, int n) {
+  const int lane = threadIdx.x & 63;
+  const unsigned long off =
+      reinterpret_cast<unsigned long>(tbl.p[min(lane, n - 1)]) -
+      reinterpret_cast<unsigned long>(tbl.p[0]);
+  return {(u32)off, (u32)(off >> 32)};
+}
+
 // rowbytes: bytes from one row of X to the next
 DEV RowOffsets stage_row_offsets(const int* __restrict__ rows, int n,
                                  int n_src, long rowbytes) {
@@ -132,19 +148,21 @@ DEV void load_rows_indexed(E (&dst)[P], const E* base, const RowOffsets& ro) {
 // MEAMED instantiations get __launch_bounds__(256, 2) via this trait so the
 // allocator may use 256 VGPRs instead of spilling, while MEDIAN/TRIMMED
 // keep the default 4-waves/SIMD occupancy.
-template <int P, int MODE, typename T, bool ROWS>
+template <int P, int MODE, typename T, int ROWS, typename... TBL>
 __global__ void
 __launch_bounds__(256, (MODE == MEAMED && P >= 64)            ? 2
                        : (ROWS && MODE == TRIMMED && P >= 64) ? 3
                                                               : 4)
 colsel_reg_kernel(const T* __restrict__ X, T* __restrict__ out,
                                   int n, long d, int f,
-                                  const int* __restrict__ rows, int n_src) {
+                                  const int* __restrict__ rows, int n_src,
+                                  TBL... tbl) {
   const long col0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long stride = (long)gridDim.x * blockDim.x;
   RowOffsets ro = {0u, 0u};
-  if (ROWS) ro = stage_row_offsets(rows, n, n_src, d * (long)sizeof(T));
-  for (long col = col0; wave_active<ROWS>(col, d); col += stride) {
+  if constexpr (ROWS == ROWS_PTRS) ro = stage_ptr_offsets(tbl..., n);
+  else if (ROWS) ro = stage_row_offsets(rows, n, n_src, d * (long)sizeof(T));
+  for (long col = col0; wave_active<(ROWS != 0)>(col, d); col += stride) {
     float v[P];
     T raw[P];
     // Load phase. Two rules keep the address walk at ONE live base:
@@ -339,7 +357,7 @@ DEV float key_to_float(u32 key16) {
 // (one 4 B/lane read, n <= 64 lanes); else the kernel runs as always. It is
 // an instantiation of its own, so that GUARD = false, which never looks at
 // `guard_G`, keeps the instruction stream it had without it.
-template <int P, int MODE, bool ROWS, bool GUARD = false>
+template <int P, int MODE, int ROWS, bool GUARD = false, typename... TBL>
 __global__ void
 __launch_bounds__(256, (MODE == MEDIAN && P >= 64) ? 5 : 4)
 colsel_pk_median_bf16(const unsigned short* __restrict__ X,
@@ -347,7 +365,8 @@ colsel_pk_median_bf16(const unsigned short* __restrict__ X,
                                       long d, int f,
                                       const int* __restrict__ rows,
                                       int n_src,
-                                      const float* __restrict__ guard_G) {
+                                      const float* __restrict__ guard_G,
+                                      TBL... tbl) {
   if (GUARD) {
     const int gl = threadIdx.x & 63;
     // |g| < inf is false for +-inf and for NaN
@@ -360,8 +379,9 @@ colsel_pk_median_bf16(const unsigned short* __restrict__ X,
   const long stride = (long)gridDim.x * blockDim.x;
   const long rowstride = d >> 1;  // in u32 units
   RowOffsets ro = {0u, 0u};
-  if (ROWS) ro = stage_row_offsets(rows, n, n_src, rowstride * (long)sizeof(u32));
-  for (long unit = unit0; wave_active<ROWS>(unit, npairs); unit += stride) {
+  if constexpr (ROWS == ROWS_PTRS) ro = stage_ptr_offsets(tbl..., n);
+  else if (ROWS) ro = stage_row_offsets(rows, n, n_src, rowstride * (long)sizeof(u32));
+  for (long unit = unit0; wave_active<(ROWS != 0)>(unit, npairs); unit += stride) {
     // ROWS: tail lanes of the last wave load a clamped (valid) pair and
     // skip the store
     const long pair = ROWS ? min(unit, npairs - 1) : unit;
@@ -1277,7 +1297,7 @@ static void colsel_generic(const T* X, T* out, int n, long d, int mode, int f,
         const int grid = capped_grid(d, block);
         by_reg_width(n, [&](auto p) {
           hipLaunchKernelGGL(
-              (colsel_reg_kernel<decltype(p)::value, MODE, T, ROWS>),
+              (colsel_reg_kernel<decltype(p)::value, MODE, T, (int)ROWS>),
               dim3(grid), dim3(block), 0, stream, X, out, n, d, f, rows,
               n_src);
         });
@@ -1321,7 +1341,7 @@ void launch_colsel<__hip_bfloat16>(const __hip_bfloat16* X,
         constexpr bool ROWS = decltype(r)::value;
         by_reg_width(n, [&](auto p) {
           hipLaunchKernelGGL(
-              (colsel_pk_median_bf16<decltype(p)::value, MODE, ROWS>),
+              (colsel_pk_median_bf16<decltype(p)::value, MODE, (int)ROWS>),
               dim3(grid), dim3(block), lds, stream, Xu, Ou, n, d, f, rows,
               n_src, (const float*)nullptr);
         });
@@ -1330,6 +1350,60 @@ void launch_colsel<__hip_bfloat16>(const __hip_bfloat16* X,
     return;
   }
   colsel_generic(X, out, n, d, mode, f, rows, n_src, stream);
+}
+
+// Row-pointer layout: the same register kernels, ROWS_PTRS instantiations.
+template <typename T>
+static void colsel_rowptrs_reg(const RowPtrTable& tbl, T* out, int n, long d,
+                               int mode, int f, hipStream_t stream) {
+  const int block = 256;
+  const int grid = capped_grid(d, block);
+  by_mode(mode, [&](auto m) {
+    constexpr int MODE = decltype(m)::value;
+    by_reg_width(n, [&](auto p) {
+      hipLaunchKernelGGL(
+          (colsel_reg_kernel<decltype(p)::value, MODE, T, ROWS_PTRS,
+                             RowPtrTable>),
+          dim3(grid), dim3(block), 0, stream, static_cast<const T*>(tbl.p[0]),
+          out, n, d, f, (const int*)nullptr, n, tbl);
+    });
+  });
+}
+
+template <>
+void launch_colsel_rowptrs<float>(const RowPtrTable& tbl, float* out, int n,
+                                  long d, int mode, int f, hipStream_t stream) {
+  colsel_rowptrs_reg(tbl, out, n, d, mode, f, stream);
+}
+
+// bf16: the packed kernel reads two adjacent columns per lane as one 4 B
+// word, legal only with every row 4 B aligned and an even d; otherwise the
+// register kernel, which needs element alignment only
+template <>
+void launch_colsel_rowptrs<__hip_bfloat16>(const RowPtrTable& tbl,
+                                           __hip_bfloat16* out, int n, long d,
+                                           int mode, int f,
+                                           hipStream_t stream) {
+  if ((d % 2) != 0 || !rowptrs_aligned(tbl, n, 4)) {
+    colsel_rowptrs_reg(tbl, out, n, d, mode, f, stream);
+    return;
+  }
+  const int block = 256;
+  const int grid = capped_grid(d >> 1, block);
+  by_mode(mode, [&](auto m) {
+    constexpr int MODE = decltype(m)::value;
+    const size_t lds =
+        MODE == MEAMED ? (size_t)block * (2 * (f + 1) + 1) * sizeof(u32) : 0;
+    by_reg_width(n, [&](auto p) {
+      hipLaunchKernelGGL(
+          (colsel_pk_median_bf16<decltype(p)::value, MODE, ROWS_PTRS, false,
+                                 RowPtrTable>),
+          dim3(grid), dim3(block), lds, stream,
+          static_cast<const unsigned short*>(tbl.p[0]),
+          reinterpret_cast<unsigned short*>(out), n, d, f, (const int*)nullptr,
+          n, (const float*)nullptr, tbl);
+    });
+  });
 }
 
 // Persistent grid: two blocks per CU (what the 69,632 B of slabs admit);
@@ -1367,7 +1441,7 @@ void launch_median_gram_bf16(const __hip_bfloat16* X, __hip_bfloat16* med,
   // has nothing to do costs a few microseconds.
   const long gwant = (long)capped_grid(d >> 1, 256);
   const long gcap = 4L * cus;
-  hipLaunchKernelGGL((colsel_pk_median_bf16<64, MEDIAN, false, true>),
+  hipLaunchKernelGGL((colsel_pk_median_bf16<64, MEDIAN, ROWS_NONE, true>),
                      dim3((unsigned)(gwant < gcap ? gwant : gcap)), dim3(256),
                      0, stream, reinterpret_cast<const unsigned short*>(X),
                      reinterpret_cast<unsigned short*>(med), n, d, 0,

@@ -90,6 +90,38 @@ void launch_coord_objective(const T* X, const float* mu, const float* p,
                             int n, long d, int mode, int f, int ntrials,
                             hipStream_t stream);
 
+// Row-pointer layout (K19): the n <= ROWPTR_MAX_N rows are n separate device
+// vectors of d elements each, named by a table of pointers that travels to
+// the kernels BY VALUE as a kernel argument (512 B): no stacked (n, d) copy,
+// no allocation, no host-to-device copy, nothing a stream capture minds.
+// Slots past n repeat a valid pointer. Rows need element alignment only;
+// the launchers pick the wider loads when rowptrs_aligned says they may.
+constexpr int ROWPTR_MAX_N = 64;
+struct RowPtrTable { const void* p[ROWPTR_MAX_N]; };
+inline bool rowptrs_aligned(const RowPtrTable& t, int n, unsigned long bytes) {
+  for (int i = 0; i < n; ++i)
+    if (reinterpret_cast<unsigned long>(t.p[i]) % bytes != 0) return false;
+  return true;
+}
+// colsel.hip: launch_colsel's register kernels over the table (same modes).
+// The packed bf16 kernel needs every pointer 4 B aligned and an even d.
+template <typename T>
+void launch_colsel_rowptrs(const RowPtrTable& rows, T* out, int n, long d,
+                           int mode, int f, hipStream_t stream);
+// rowptrs.hip: partials are ADDED into the caller-zeroed (n, n) G; a second
+// launch mirrors the upper triangle, so G is symmetric bit for bit. 16 B
+// aligned pointers take vector loads, others the element loads.
+void gram_rowptrs_geometry(long d, int elem_bytes, int cus, long& blocks,
+                           long& chunks_per_block);
+template <typename T>
+void launch_gram_rowptrs(const RowPtrTable& rows, float* G, int n, long d,
+                         hipStream_t stream);
+// rowptrs.hip: the mean of rows idx[0 .. k) of the table, f32 accumulation;
+// idx is an int32 device vector (clamped to [0, n)).
+template <typename T>
+void launch_mean_rows_rowptrs(const RowPtrTable& rows, int n, const int* idx,
+                              int k, T* out, long d, hipStream_t stream);
+
 // rsel.hip: streaming radix-select engine for large n, same modes.
 // `state` is caller-zeroed d*4 u32 scratch; `med` is a d-float scratch,
 // read only by mode 2 (may be null otherwise)

@@ -55,9 +55,33 @@ def _colsel_rows(X: torch.Tensor, mode: int, f: int, rows: torch.Tensor):
     return None
 
 
+# Row lists (K19): ``median``, ``trimmed_mean``, ``mean_of_medians``, ``gram``,
+# ``mean_rows``, ``multi_krum`` and ``krum`` also take, in place of the (n, d)
+# matrix, a list or tuple of n <= ROW_LIST_MAX_N flat device tensors (one
+# dtype, f32 or bf16, one length, one device, each contiguous) and read the
+# rows where they are: the kernels get the n pointers as a by-value kernel
+# argument, so no (n, d) copy is stacked and nothing is allocated but the
+# result (csrc/rowptrs.hip, the ROWS_PTRS kernels of csrc/colsel.hip). The
+# binding checks the list. Measured on MI355X against stacking first
+# (benchmarks/RESULTS_MI355X_rows.md): the public call in place took 0.21-0.92
+# of the stacked call's time at EVERY measured shape (64 x 64K, 1M, 16M and
+# 33 x 16M, bf16 and f32), so the route has no d threshold.
+ROW_LIST_MAX_N = 64
+
+
+def _row_list(X) -> bool:
+    return isinstance(X, (list, tuple))
+
+
+def _colsel_row_list(rows, mode: int, f: int) -> torch.Tensor:
+    return _hip.require().colsel(list(rows), mode, int(f))
+
+
 def median(X: torch.Tensor, rows: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``rows`` (m distinct row indices) restricts the statistic to those
     rows, as if on X[rows]; same for trimmed_mean and mean_of_medians."""
+    if _row_list(X):
+        return _colsel_row_list(X, _COLSEL_MEDIAN, 0)
     if rows is not None:
         out = _colsel_rows(X, _COLSEL_MEDIAN, 0, rows) if _gpu(X) else None
         return out if out is not None else median(X[rows.long()])
@@ -69,6 +93,8 @@ def median(X: torch.Tensor, rows: Optional[torch.Tensor] = None) -> torch.Tensor
 def trimmed_mean(
     X: torch.Tensor, f: int, rows: Optional[torch.Tensor] = None
 ) -> torch.Tensor:
+    if _row_list(X):
+        return _colsel_row_list(X, _COLSEL_TRIMMED, f)
     if rows is not None:
         out = _colsel_rows(X, _COLSEL_TRIMMED, f, rows) if _gpu(X) else None
         return out if out is not None else trimmed_mean(X[rows.long()], f)
@@ -80,6 +106,8 @@ def trimmed_mean(
 def mean_of_medians(
     X: torch.Tensor, f: int, rows: Optional[torch.Tensor] = None
 ) -> torch.Tensor:
+    if _row_list(X):
+        return _colsel_row_list(X, _COLSEL_MEAMED, f)
     if rows is not None:
         out = _colsel_rows(X, _COLSEL_MEAMED, f, rows) if _gpu(X) else None
         return out if out is not None else mean_of_medians(X[rows.long()], f)
@@ -93,6 +121,8 @@ def mean_of_medians(
 
 def gram(X: torch.Tensor) -> torch.Tensor:
     """X @ X.T with f32 accumulation; MFMA split-K kernel on device."""
+    if _row_list(X):
+        return _hip.require().gram(list(X))
     if _gpu(X):
         return _hip.require().gram(X.contiguous())
     Xf = X.float()
@@ -265,12 +295,15 @@ def multi_krum_scores(X: torch.Tensor, f: int) -> torch.Tensor:
 
 
 def multi_krum(X: torch.Tensor, f: int, q: int) -> torch.Tensor:
-    if _gpu(X):
+    if _row_list(X) or _gpu(X):
         return mean_rows(X, krum_winners_from_gram(gram(X), f, q))
     return F.multi_krum(X, f, q)
 
 
 def krum(X: torch.Tensor, f: int) -> torch.Tensor:
+    if _row_list(X):
+        # the q = 1 mean is the winner itself, and it never visits the host
+        return mean_rows(X, krum_winners_from_gram(gram(X), f, 1))
     if _gpu(X) and X.shape[0] <= 512:
         idx = krum_winners_from_gram(gram(X), f, 1)
         return X[idx.long()[0]].clone()
@@ -294,6 +327,9 @@ def bulyan(X: torch.Tensor, f: int) -> torch.Tensor:
 
 def mean_rows(X: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """Mean of the selected rows, f32 accumulation (K10 gather-mean)."""
+    if _row_list(X):
+        idx32 = idx.to(device=X[0].device, dtype=torch.int32).contiguous()
+        return _hip.require().mean_rows(list(X), idx32)
     if _gpu(X):
         return _hip.require().mean_rows(X.contiguous(), idx.to(torch.int32))
     return X.float()[idx].mean(dim=0).to(X.dtype)

@@ -8,7 +8,8 @@ shape (or parameter-list structure) only at the boundary.
 """
 from __future__ import annotations
 
-from typing import Any, List, Tuple
+import os
+from typing import Any, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -102,6 +103,47 @@ def stack_gradients(
     if device is not None:
         X = X.to(device)
     return X, like
+
+
+# Row cap of the row-pointer kernels (ROWPTR_MAX_N in hip/csrc/launchers.h).
+ROWS_IN_PLACE_MAX_N = 64
+
+# BYZPY_ROWS_IN_PLACE=stack forces the stacked route (A/B runs)
+_ROWS_IN_PLACE_ENV = "BYZPY_ROWS_IN_PLACE"
+
+
+def rows_in_place(gradients: Any) -> Optional[List[torch.Tensor]]:
+    """The flat row views of ``gradients`` when the aggregation can read them
+    where they are, else None (and the caller stacks, as always). It can for
+    a list or tuple of 1 to ROWS_IN_PLACE_MAX_N device tensors, f32 or bf16,
+    of one dtype, one device and one non-zero numel, each contiguous, so
+    that ``reshape(-1)`` is a view: no (n, d) copy is made. Param lists,
+    ndarrays, mixed dtypes, CPU tensors, a 2-D tensor and longer lists are
+    declined."""
+    if os.environ.get(_ROWS_IN_PLACE_ENV, "") == "stack":
+        return None
+    if not isinstance(gradients, (list, tuple)):
+        return None
+    if not 1 <= len(gradients) <= ROWS_IN_PLACE_MAX_N:
+        return None
+    g0 = gradients[0]
+    if not (
+        isinstance(g0, torch.Tensor)
+        and g0.is_cuda
+        and g0.dtype in (torch.float32, torch.bfloat16)
+        and g0.numel() >= 1
+    ):
+        return None
+    for g in gradients:
+        if not (
+            isinstance(g, torch.Tensor)
+            and g.dtype == g0.dtype
+            and g.device == g0.device
+            and g.numel() == g0.numel()
+            and g.is_contiguous()
+        ):
+            return None
+    return [g.detach().reshape(-1) for g in gradients]
 
 
 def to_like(vec: torch.Tensor, like: LikeTemplate) -> Any:
