@@ -404,7 +404,18 @@ class AFAReputation:
 
 class GeometricMedian(Aggregator):
     """Weiszfeld fixed point; barriered per-iteration fan-out on CPU pools
-    (reference geometric_median.py:106-158), fused kernels on GPU."""
+    (reference geometric_median.py:106-158), fused kernels on GPU.
+
+    ``solver="gram"`` (opt-in) runs the whole loop, convergence test
+    included, in coefficient space on the Gram in one device launch: two
+    passes over X whatever the step count (three or four from the median
+    init, whose first step uses real distances and is not tested for
+    convergence), no host poll, and device row lists read in place with
+    ``init="mean"``. Its limit: distances come from an f32 Gram, so a row
+    closer to the centre than roughly 2^-11 of its own norm is not resolved
+    and its weight saturates at that floor, not at ``eps``. A row that holds
+    inf or NaN gets weight 0 and is left out. The CPU pool fan-out is the
+    iterative rule under either solver."""
 
     name = "geometric-median"
     supports_barriered_subtasks = True
@@ -419,11 +430,18 @@ class GeometricMedian(Aggregator):
         init: str = "median",
         chunk_size: int = 32,
         fixed_iters: "int | None" = None,
+        solver: str = "iterative",
     ) -> None:
         if tol <= 0 or max_iter <= 0 or eps <= 0:
             raise ValueError("tol, max_iter, eps must be > 0")
         if init not in {"median", "mean"}:
             raise ValueError("init must be 'median' or 'mean'")
+        if solver not in D.SOLVERS:
+            raise ValueError("solver must be 'iterative' or 'gram'")
+        self.solver = solver
+        if solver == "gram" and init == "mean":
+            # device row lists are read where they are: no stacked copy
+            self._aggregate_rows = self._aggregate
         if fixed_iters is not None and fixed_iters <= 0:
             raise ValueError("fixed_iters must be > 0")
         self.tol, self.max_iter, self.eps = float(tol), int(max_iter), float(eps)
@@ -438,7 +456,7 @@ class GeometricMedian(Aggregator):
     def _aggregate(self, X: torch.Tensor) -> torch.Tensor:
         return D.geometric_median(
             X, tol=self.tol, max_iter=self.max_iter, eps=self.eps,
-            init=self.init, fixed_iters=self.fixed_iters
+            init=self.init, fixed_iters=self.fixed_iters, solver=self.solver
         )
 
     async def run_barriered_subtasks(self, ctx: OpContext, **inputs: Any) -> Any:

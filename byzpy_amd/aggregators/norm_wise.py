@@ -23,7 +23,15 @@ from byzpy_amd.utils.flatten import to_like
 
 class CenteredClipping(Aggregator):
     """v <- v + (1/n) sum clip(x_i - v, c_tau), M iterations (Karimireddy
-    et al. 2021); barriered row-chunk fan-out per iteration on CPU pools."""
+    et al. 2021); barriered row-chunk fan-out per iteration on CPU pools.
+
+    ``solver="gram"`` (opt-in, ``init`` "mean" or "zero") runs the M steps
+    in coefficient space on the Gram in one device launch: two passes over X
+    whatever M is, and device row lists read in place. Its limit: distances
+    come from an f32 Gram, so a row closer to v than roughly 2^-11 of its own
+    norm is not resolved and its clipping factor saturates at that floor,
+    not at ``eps``. A row that holds inf or NaN gets factor 0 and is left
+    out. The CPU pool fan-out is the iterative rule under either solver."""
 
     name = "centered-clipping"
     supports_barriered_subtasks = True
@@ -37,6 +45,7 @@ class CenteredClipping(Aggregator):
         eps: float = 1e-12,
         init: str = "mean",
         chunk_size: int = 32,
+        solver: str = "iterative",
     ) -> None:
         if c_tau < 0:
             raise ValueError("c_tau must be >= 0")
@@ -44,13 +53,25 @@ class CenteredClipping(Aggregator):
             raise ValueError("M and eps must be > 0")
         if init not in {"mean", "median", "zero"}:
             raise ValueError("init must be one of {'mean','median','zero'}")
+        if solver not in D.SOLVERS:
+            raise ValueError("solver must be 'iterative' or 'gram'")
+        if solver == "gram" and init == "median":
+            raise ValueError(
+                "solver='gram' needs init 'mean' or 'zero': from the median v "
+                "keeps a component outside the span of the rows"
+            )
+        self.solver = solver
+        if solver == "gram":
+            # device row lists are read where they are: no stacked copy
+            self._aggregate_rows = self._aggregate
         self.c_tau, self.M, self.eps = float(c_tau), int(M), float(eps)
         self.init = init
         self.chunk_size = int(chunk_size)
 
     def _aggregate(self, X: torch.Tensor) -> torch.Tensor:
         return D.centered_clipping(
-            X, c_tau=self.c_tau, M=self.M, eps=self.eps, init=self.init
+            X, c_tau=self.c_tau, M=self.M, eps=self.eps, init=self.init,
+            solver=self.solver,
         )
 
     async def run_barriered_subtasks(self, ctx: OpContext, **inputs: Any) -> Any:

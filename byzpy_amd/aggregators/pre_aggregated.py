@@ -17,6 +17,7 @@ from byzpy_amd.aggregators.coordinate_wise import (
     CoordinateWiseMedian,
     CoordinateWiseTrimmedMean,
 )
+from byzpy_amd.aggregators.geometric_wise import GeometricMedian
 from byzpy_amd.hip import dispatch as D
 
 
@@ -25,8 +26,10 @@ class PreAggregated(Aggregator):
 
     A pre-aggregator with a ``membership(X)`` method (NearestNeighborMixing,
     Bucketing) in front of CoordinateWiseMedian or CoordinateWiseTrimmedMean
-    takes the fused device route where ``D.mixed_colsel_fused_ok(X)``;
-    everything else is
+    takes the fused device route where ``D.mixed_colsel_fused_ok(X)``; in
+    front of ``GeometricMedian(solver="gram", init="mean")`` the rule runs on
+    the mixed Gram W G W^T and the coefficients pull back as W^T a, so no
+    mixed matrix is formed on any device; everything else is
     ``aggregator._aggregate(pre_aggregator._pre_aggregate(X))``."""
 
     name = "pre-aggregated"
@@ -43,4 +46,21 @@ class PreAggregated(Aggregator):
                 return D.mixed_median(X, pre.membership(X))
             if type(agg) is CoordinateWiseTrimmedMean:
                 return D.mixed_trimmed_mean(X, pre.membership(X), agg.f)
+        if (
+            hasattr(pre, "membership")
+            and type(agg) is GeometricMedian
+            and agg.solver == "gram"
+            and agg.init == "mean"
+        ):
+            # Gram of Y = W X is W G W^T and coefficients pull back as W^T a:
+            # the rule runs on the mixed rows with no mixed matrix (K20)
+            G = D.solver_gram(X)
+            if hasattr(pre, "membership_from_gram"):
+                mix = pre.membership_from_gram(G)
+            else:
+                mix = pre.membership(X)
+            return D.mixed_geometric_median(
+                X, mix, gram=G, tol=agg.tol, max_iter=agg.max_iter,
+                eps=agg.eps, fixed_iters=agg.fixed_iters,
+            )
         return agg._aggregate(pre._pre_aggregate(X))

@@ -557,6 +557,102 @@ torch::Tensor mean_rows_rowlist(std::vector<torch::Tensor> rows,
   return out;
 }
 
+// -- fixed points on the Gram (K20) -------------------------------------------
+
+void check_coeffs(const torch::Tensor& coeffs, int64_t n,
+                  const torch::Device& device) {
+  TORCH_CHECK(coeffs.dim() == 1, "coeffs: expected one dimension, got ",
+              coeffs.dim());
+  check_f32_vector(coeffs, n, "coeffs");
+  TORCH_CHECK(coeffs.device() == device, "coeffs: expected the rows' device");
+}
+
+// mean_rows(X, coeffs=a): out = sum_i a[i] X[i] in X's dtype (rowptrs.hip).
+// Not normalised; rows with a[i] == 0 are not read. n <= GRAMFP_MAX_N.
+torch::Tensor combine_rows(torch::Tensor X, torch::Tensor coeffs) {
+  check_matrix(X);
+  const int64_t n = X.size(0);
+  const long d = (long)X.size(1);
+  TORCH_CHECK(n >= 1 && n <= GRAMFP_MAX_N, "mean_rows(coeffs=) supports ",
+              "1 <= n <= ", GRAMFP_MAX_N, ", got ", n);
+  TORCH_CHECK(d >= 1, "mean_rows(coeffs=): expected at least one column");
+  check_coeffs(coeffs, n, X.device());
+  auto out = torch::empty({d}, X.options());
+  by_dtype(X, [&](auto tag) {
+    using T = TAG_T(tag);
+    launch_combine_rows<T>(ptr<T>(X), RowPtrTable{}, f32(coeffs), (int)n,
+                           ptr<T>(out), d, cur_stream());
+  });
+  return out;
+}
+
+// mean_rows(rows, coeffs=a): the same over a list of n <= 64 1-D device rows,
+// bitwise what the stacked matrix gives.
+torch::Tensor combine_rows_rowlist(std::vector<torch::Tensor> rows,
+                                   torch::Tensor coeffs) {
+  const RowPtrTable tbl = check_row_list(rows, "mean_rows");
+  const int n = (int)rows.size();
+  check_coeffs(coeffs, n, rows[0].device());
+  const long d = (long)rows[0].numel();
+  auto out = torch::empty({d}, rows[0].options());
+  by_dtype(rows[0], [&](auto tag) {
+    using T = TAG_T(tag);
+    launch_combine_rows<T>(nullptr, tbl, f32(coeffs), n, ptr<T>(out), d,
+                           cur_stream());
+  });
+  return out;
+}
+
+std::vector<torch::Tensor> gram_fixed_point(const torch::Tensor& G,
+                                            const torch::Tensor& a0, int rule,
+                                            double eps, double tol,
+                                            double c_tau, int64_t iters,
+                                            const char* op) {
+  check_gram(G, "G");
+  const int64_t n = G.size(0);
+  TORCH_CHECK(n >= 1 && n <= GRAMFP_MAX_N, op, "(G, a0) supports 1 <= n <= ",
+              GRAMFP_MAX_N, ", got ", n);
+  TORCH_CHECK(a0.dim() == 1, "a0: expected one dimension, got ", a0.dim());
+  check_f32_vector(a0, n, "a0");
+  TORCH_CHECK(a0.device() == G.device(), "a0: expected G's device");
+  TORCH_CHECK(eps > 0.0 && eps < INFINITY, "eps: expected a finite value > 0, ",
+              "got ", eps);
+  TORCH_CHECK(tol >= 0.0 && tol < INFINITY, "tol: expected a finite value ",
+              ">= 0, got ", tol);
+  TORCH_CHECK(c_tau >= 0.0 && c_tau < INFINITY, "c_tau: expected a finite ",
+              "value >= 0, got ", c_tau);
+  TORCH_CHECK(iters >= 0 && iters <= INT_MAX, "iters: expected 0 <= iters <= ",
+              INT_MAX, ", got ", iters);
+  auto a = torch::empty({n}, f32_like(G));
+  auto steps = torch::empty({}, i32_like(G));
+  auto shift2 = torch::empty({}, f32_like(G));
+  launch_gram_fixed_point(f32(G), f32(a0), (int)n, rule, eps, tol * tol, c_tau,
+                          (int)iters, f32(a), i32(steps), f32(shift2),
+                          cur_stream());
+  return {a, steps, shift2};
+}
+
+// weiszfeld_iter(G, a0, eps=, tol=, iters=): the whole Weiszfeld loop in
+// coefficient space on the f32 Gram (gramfp.hip), one launch. Returns
+// (a f32 (n,), steps int32 (), shift2 f32 ()): the coefficients of the
+// iterate sum_i a_i x_i, the steps taken (< iters when a step moved by
+// <= tol; tol = 0 never stops early) and the last step's squared shift.
+// No host sync.
+std::vector<torch::Tensor> weiszfeld_gram(torch::Tensor G, torch::Tensor a0,
+                                          double eps, double tol,
+                                          int64_t iters) {
+  return gram_fixed_point(G, a0, GRAMFP_WEISZFELD, eps, tol, 0.0, iters,
+                          "weiszfeld_iter");
+}
+
+// cc_iter(G, a0, c_tau=, eps=, iters=): exactly `iters` centered-clipping
+// steps in coefficient space; returns a f32 (n,). No host sync.
+torch::Tensor cc_gram(torch::Tensor G, torch::Tensor a0, double c_tau,
+                      double eps, int64_t iters) {
+  return gram_fixed_point(G, a0, GRAMFP_CC, eps, 0.0, c_tau, iters,
+                          "cc_iter")[0];
+}
+
 // Fused Krum selection: Gram -> q winner indices (one kernel, replaces
 // the D2-build + two topk torch chains whose launch overhead caps the
 // d-sharded multi-GPU scaling).
@@ -977,6 +1073,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mean_rows", &mean_rows_rowlist,
         "mean of rows[idx[i]] over a list of n <= 64 1-D device rows (K19)",
         py::arg("rows"), py::arg("idx"));
+  m.def("mean_rows", &combine_rows,
+        "sum_i coeffs[i] X[i], rows under a zero coefficient not read (K20)",
+        py::arg("X"), py::kw_only(), py::arg("coeffs"));
+  m.def("mean_rows", &combine_rows_rowlist,
+        "the same over a list of n <= 64 1-D device rows (K20)",
+        py::arg("rows"), py::kw_only(), py::arg("coeffs"));
   m.def("group_mean_rows", &group_mean_rows);
   m.def("bucket_mean", &bucket_mean);
   m.def("gram", &gram);
@@ -996,10 +1098,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("caf_colsum", &caf_colsum, py::arg("X"), py::arg("a"),
         py::arg("mu") = c10::nullopt, py::arg("scale") = c10::nullopt);
   m.def("weiszfeld_iter", &weiszfeld_iter);
+  m.def("weiszfeld_iter", &weiszfeld_gram,
+        "the Weiszfeld loop on the Gram (K20): (a, steps, shift2)",
+        py::arg("G"), py::arg("a0"), py::kw_only(), py::arg("eps"),
+        py::arg("tol"), py::arg("iters"));
   m.def("weiszfeld_iter_grouped", &weiszfeld_iter_grouped,
         "one Weiszfeld iteration for G independent (m, d) groups");
   m.def("weiszfeld_apply", &weiszfeld_apply);
   m.def("cc_iter", &cc_iter);
+  m.def("cc_iter", &cc_gram,
+        "the centered-clipping loop on the Gram (K20): a", py::arg("G"),
+        py::arg("a0"), py::kw_only(), py::arg("c_tau"), py::arg("eps"),
+        py::arg("iters"));
   m.def("cc_apply", &cc_apply);
   m.def("mda_search", &mda_search, "exact min-diameter subset (host DFS)");
   m.def("smea_select", &smea_select, "device SMEA subset selection (K11)");

@@ -122,6 +122,33 @@ template <typename T>
 void launch_mean_rows_rowptrs(const RowPtrTable& rows, int n, const int* idx,
                               int k, T* out, long d, hipStream_t stream);
 
+// gramfp.hip (K20): the Weiszfeld (rule GRAMFP_WEISZFELD) or centered-clipping
+// (GRAMFP_CC) fixed point solved in coefficient space on the f32 Gram G (n, n),
+// one workgroup, one launch for the whole loop. The iterate is z = sum_i a_i
+// x_i; its distances are d_i = max(sqrt(max(G_ii - 2 (G a)_i + a^T G a, 0)),
+// eps). Weiszfeld: a' = w / sum w, w_i = 1 / d_i, at most `iters` steps, ended
+// early by the first step with (a' - a)^T G (a' - a) <= tol2 when tol2 > 0.
+// Clipping: a' = (1 - sum c / n) a + c / n, c_i = min(1, c_tau / d_i), exactly
+// `iters` steps. A row whose G_ii is not finite is dead: coefficient 0, in no
+// sum. Everything past the f32 entries is f64 in a fixed order: bitwise
+// repeatable. Writes a (n,) f32, the step count and the last step's squared
+// shift. 1 <= n <= GRAMFP_MAX_N, iters >= 0. No host sync.
+constexpr int GRAMFP_MAX_N = 128;
+constexpr int GRAMFP_WEISZFELD = 0;
+constexpr int GRAMFP_CC = 1;
+void launch_gram_fixed_point(const float* G, const float* a0, int n, int rule,
+                             double eps, double tol2, double c_tau, int iters,
+                             float* a, int* steps, float* shift2,
+                             hipStream_t stream);
+// rowptrs.hip (K20): out = sum_i coef[i] x_i, not normalised, f32 accumulation
+// in row order, out in T. Rows with coef[i] == 0 are never read. X null: the
+// rows are the table's (n <= ROWPTR_MAX_N); else rows of the contiguous (n, d)
+// X (n <= GRAMFP_MAX_N). Both add in one order: the same values give the same
+// bits whichever way they are laid out.
+template <typename T>
+void launch_combine_rows(const T* X, const RowPtrTable& rows, const float* coef,
+                         int n, T* out, long d, hipStream_t stream);
+
 // rsel.hip: streaming radix-select engine for large n, same modes.
 // `state` is caller-zeroed d*4 u32 scratch; `med` is a d-float scratch,
 // read only by mode 2 (may be null otherwise)

@@ -1,6 +1,8 @@
 // Kernels over n <= 64 rows that live in n separate device vectors (K19):
-// the Gram G = X X^T and the mean of selected rows (the column-selection
-// kernels of this layout are ROWS_PTRS instantiations in colsel.hip). The
+// the Gram G = X X^T, the mean of selected rows and the coefficient combine
+// sum_i a_i x_i (K20; the same kernel text also serves a contiguous matrix of
+// n <= 128 rows). The column-selection kernels of this layout are ROWS_PTRS
+// instantiations in colsel.hip. The
 // rows are named by a table of pointers passed BY VALUE as a kernel argument
 // (RowPtrTable, 512 B), so nothing is stacked, nothing is allocated and
 // nothing is copied to the device before the launch. Built without
@@ -275,6 +277,105 @@ mean_rowptrs_kernel(RowPtrTable tbl, int n, const int* __restrict__ idx,
   }
 }
 
+// ---------------------------------------------------------------------------
+// Combine (K20): out = sum_i coef[i] x_i with the f32 coefficients on the
+// device. Not a mean: nothing is normalised, coefficients may be negative or
+// zero. Each block first compacts the rows with coef != 0 into LDS (pointer
+// and coefficient, in row order), so a row under a zero coefficient (a dead
+// row full of inf or NaN) is never read, and the column loop walks LDS only.
+// One thread owns 16 B of consecutive coordinates per grid-stride step, four
+// row loads in flight, and adds acc = fma(c_k, x_k, acc) strictly in row
+// order. The vector loop runs when every compacted row and `out` are 16 B
+// aligned (a block-wide vote); the d % V coordinates past the last full
+// vector, and everything otherwise, go one element per thread through the
+// same fma chain. Rows = the table or a contiguous matrix: one kernel text,
+// so a list and its stacked matrix give the same bits.
+// ---------------------------------------------------------------------------
+
+constexpr int CMB_THREADS = 256;
+constexpr int CMB_MAX_BLOCKS = 4096;
+static_assert(CMB_THREADS >= GRAMFP_MAX_N, "one thread per row compacts");
+
+struct TableRows {
+  RowPtrTable t;
+  DEV const char* row(int i) const {
+    return reinterpret_cast<const char*>(t.p[i]);
+  }
+};
+struct MatrixRows {
+  const char* base;
+  long row_bytes;
+  DEV const char* row(int i) const { return base + (long)i * row_bytes; }
+};
+
+template <typename T, typename Rows>
+__global__ void __launch_bounds__(CMB_THREADS)
+combine_rows_kernel(Rows src, const float* __restrict__ coef, int n,
+                    T* __restrict__ out, long d) {
+  constexpr int V = 16 / (int)sizeof(T);
+  __shared__ const char* rowp[GRAMFP_MAX_N];
+  __shared__ float cf[GRAMFP_MAX_N];
+  __shared__ int nzf[GRAMFP_MAX_N];
+  const int tid = threadIdx.x;
+
+  float c = 0.0f;
+  const char* p = nullptr;
+  bool nz = false;
+  if (tid < n) {
+    c = coef[tid];
+    nz = c != 0.0f;
+    if (nz) p = src.row(tid);
+  }
+  if (tid < GRAMFP_MAX_N) nzf[tid] = nz ? 1 : 0;
+  const int m = __syncthreads_count(nz);
+  const bool misaligned =
+      nz && reinterpret_cast<unsigned long>(p) % 16 != 0;
+  const bool vec = __syncthreads_or(misaligned) == 0 &&
+                   reinterpret_cast<unsigned long>(out) % 16 == 0;
+  if (nz) {
+    int before = 0;
+    for (int j = 0; j < tid; ++j) before += nzf[j];
+    rowp[before] = p;
+    cf[before] = c;
+  }
+  __syncthreads();
+
+  const long start = (long)blockIdx.x * CMB_THREADS + tid;
+  const long stride = (long)gridDim.x * CMB_THREADS;
+  const long dv = vec ? d / V : 0;
+  for (long jv = start; jv < dv; jv += stride) {
+    const long off = jv * 16;
+    auto run = [&](int k) {
+      return *reinterpret_cast<const gr_u32x4*>(rowp[k] + off);
+    };
+    auto add = [&](int k, const gr_u32x4 w, float (&acc)[V]) {
+      float x[V];
+      unpack_run<T>(w, x);
+      const float ck = cf[k];
+#pragma unroll
+      for (int e = 0; e < V; ++e) acc[e] = fmaf(ck, x[e], acc[e]);
+    };
+    float acc[V] = {0};
+    int k = 0;
+    for (; k + 4 <= m; k += 4) {
+      const gr_u32x4 w0 = run(k), w1 = run(k + 1), w2 = run(k + 2),
+                     w3 = run(k + 3);
+      add(k, w0, acc);
+      add(k + 1, w1, acc);
+      add(k + 2, w2, acc);
+      add(k + 3, w3, acc);
+    }
+    for (; k < m; ++k) add(k, run(k), acc);
+    *reinterpret_cast<gr_u32x4*>(out + jv * V) = pack_run<T>(acc);
+  }
+  for (long j = dv * V + start; j < d; j += stride) {
+    float acc = 0.0f;
+    for (int k = 0; k < m; ++k)
+      acc = fmaf(cf[k], to_f<T>(reinterpret_cast<const T*>(rowp[k])[j]), acc);
+    out[j] = from_f<T>(acc);
+  }
+}
+
 // G[i][j] = G[j][i] for i > j, once every partial has landed
 __global__ void gram_rowptrs_mirror_kernel(float* __restrict__ G, int n) {
   for (int i = threadIdx.x; i < n * n; i += blockDim.x) {
@@ -335,3 +436,22 @@ void launch_mean_rows_rowptrs(const RowPtrTable& rows, int n, const int* idx,
                        stream, rows, n, idx, k, out, d);
 }
 INSTANTIATE_LAUNCHER(launch_mean_rows_rowptrs)
+
+template <typename T>
+void launch_combine_rows(const T* X, const RowPtrTable& rows, const float* coef,
+                         int n, T* out, long d, hipStream_t stream) {
+  constexpr int V = 16 / (int)sizeof(T);
+  const long want = (d / V + CMB_THREADS) / CMB_THREADS;
+  const dim3 grid((unsigned)(want < CMB_MAX_BLOCKS ? want : CMB_MAX_BLOCKS));
+  if (X == nullptr)
+    hipLaunchKernelGGL((combine_rows_kernel<T, TableRows>), grid,
+                       dim3(CMB_THREADS), 0, stream, TableRows{rows}, coef, n,
+                       out, d);
+  else
+    hipLaunchKernelGGL((combine_rows_kernel<T, MatrixRows>), grid,
+                       dim3(CMB_THREADS), 0, stream,
+                       MatrixRows{reinterpret_cast<const char*>(X),
+                                  d * (long)sizeof(T)},
+                       coef, n, out, d);
+}
+INSTANTIATE_LAUNCHER(launch_combine_rows)

@@ -673,6 +673,207 @@ def cge(X: torch.Tensor, f: int) -> torch.Tensor:
     return F.cge(X, f)
 
 
+# -- fixed points on the Gram (K20) -------------------------------------------
+#
+# ``solver="gram"`` of geometric_median and centered_clipping. A Weiszfeld
+# update is a convex combination of the rows whatever the centre is, and a
+# clipping update keeps v in the row span when v starts as the mean or zero.
+# So the iterate is z = sum_i a_i x_i, and with G = X X^T
+#   ||x_i - z||^2 = G_ii - 2 (G a)_i + a^T G a,
+#   ||z' - z||^2  = (a' - a)^T G (a' - a):
+# the whole loop, convergence test included, runs on n numbers in one launch
+# (csrc/gramfp.hip) and X is read twice in all, once for the Gram and once
+# to form sum_i a_i x_i (``mean_rows(X, coeffs=a)``, csrc/rowptrs.hip),
+# against two passes per step for the iterative kernels. Opt-in, because the
+# distances come from an f32 Gram: a row closer to the centre than roughly
+# 2^-11 of its own norm is not resolved (the cancellation in
+# G_ii - 2 u_i + q leaves an error of about 2^-23 ||x_i||^2 in d_i^2), and its
+# weight saturates at that floor, not at eps. A row with a non-finite G_ii is
+# dead: coefficient 0, never read by the combine.
+#
+# The device route takes f32 / bf16 device matrices of n <= GRAMFP_MAX_N rows
+# and row lists (n <= ROW_LIST_MAX_N); everything else runs the same
+# arithmetic as f64 torch ops (F.gram_fixed_point), which may sync.
+
+# Row cap of weiszfeld_iter(G, a0, ...), cc_iter(G, a0, ...) and
+# mean_rows(X, coeffs=) (GRAMFP_MAX_N in csrc/launchers.h).
+GRAMFP_MAX_N = 128
+SOLVERS = ("iterative", "gram")
+
+
+def _check_solver(solver: str) -> None:
+    if solver not in SOLVERS:
+        raise ValueError("solver must be 'iterative' or 'gram'")
+
+
+def _gramfp_fused(X) -> bool:
+    if _row_list(X):
+        return len(X) <= ROW_LIST_MAX_N and all(r.is_cuda for r in X)
+    return (
+        _gpu(X)
+        and X.dtype in (torch.float32, torch.bfloat16)
+        and 1 <= X.shape[0] <= GRAMFP_MAX_N
+        and X.shape[1] >= 1
+    )
+
+
+def gram_fixed_point(
+    G: torch.Tensor,
+    a0: torch.Tensor,
+    *,
+    rule: str,
+    iters: int,
+    eps: float = 1e-12,
+    tol: float = 0.0,
+    c_tau: float = 0.0,
+):
+    """(a, steps, shift2) of F.gram_fixed_point: one launch and no host sync
+    for an f32 device Gram of n <= GRAMFP_MAX_N rows (steps and shift2 stay
+    device scalars), the f64 torch loop otherwise."""
+    if _gpu(G) and G.dtype == torch.float32 and G.shape[0] <= GRAMFP_MAX_N:
+        ext = _hip.require()
+        a0 = a0.to(device=G.device, dtype=torch.float32).contiguous()
+        if rule == "weiszfeld":
+            return tuple(ext.weiszfeld_iter(
+                G.contiguous(), a0, eps=float(eps), tol=float(tol), iters=int(iters)
+            ))
+        if rule != "cc":
+            raise ValueError("rule must be 'weiszfeld' or 'cc'")
+        a = ext.cc_iter(
+            G.contiguous(), a0, c_tau=float(c_tau), eps=float(eps), iters=int(iters)
+        )
+        return a, int(iters), None
+    return F.gram_fixed_point(
+        G, a0, rule=rule, iters=iters, eps=eps, tol=tol, c_tau=c_tau
+    )
+
+
+def combine_rows(X, a: torch.Tensor) -> torch.Tensor:
+    """sum_i a_i x_i in X's dtype, not normalised; rows with a_i == 0 are not
+    read. f32 accumulation in row order on the device (a list and its stacked
+    matrix give the same bits), f64 elsewhere."""
+    if _gramfp_fused(X):
+        dev = X[0].device if _row_list(X) else X.device
+        a32 = a.to(device=dev, dtype=torch.float32).contiguous()
+        rows = list(X) if _row_list(X) else X.contiguous()
+        return _hip.require().mean_rows(rows, coeffs=a32)
+    keep = a != 0
+    return (a[keep].double() @ X[keep].double()).to(X.dtype)
+
+
+def solver_gram(X) -> torch.Tensor:
+    if _gramfp_fused(X):
+        return gram(X)
+    Xd = X.double()
+    return Xd @ Xd.T
+
+
+def _live_uniform(G: torch.Tensor) -> torch.Tensor:
+    """The coefficients of the mean of the rows with a finite G_ii."""
+    live = torch.isfinite(torch.diagonal(G)).to(G.dtype)
+    return live / live.sum().clamp(min=1.0)
+
+
+def mixed_gram(G: torch.Tensor, mix: torch.Tensor):
+    """(G_Y, W) for the mixed rows Y = W X, W = mix / its row counts in f64:
+    G_Y = W G W^T in G's dtype, and coefficients a over the rows of Y pull
+    back to W^T a over the rows of X. A mixed row that contains a dead row of
+    X (non-finite G_ii) gets an infinite diagonal entry, so it is dead too."""
+    W = mix.to(device=G.device, dtype=torch.float64)
+    W = W / W.sum(dim=1, keepdim=True)
+    Gd = G.double()
+    dead = ~torch.isfinite(torch.diagonal(Gd))
+    Gd = torch.where(torch.isfinite(Gd), Gd, torch.zeros_like(Gd))
+    GY = W @ Gd @ W.T
+    dead_y = (W * dead.double()[None, :]).sum(dim=1) > 0
+    inf = torch.full_like(dead_y, float("inf"), dtype=torch.float64)
+    GY = GY + torch.diag(torch.where(dead_y, inf, torch.zeros_like(inf)))
+    return GY.to(G.dtype), W
+
+
+def _geometric_median_gram(
+    X, *, tol, max_iter, eps, init, fixed_iters, init_z, mix=None, G=None
+) -> torch.Tensor:
+    """geometric_median(solver="gram"). ``init="mean"``: a0 is uniform over
+    the live rows. ``init="median"`` / ``init_z``: z0 is outside the span but
+    the first update is not, so that step uses real distances
+    (row_center_sqdists, one more pass) and the solver runs the rest; its
+    shift is not tested. ``mix`` (m, n) runs the rule on the mixed rows
+    (mixed_gram) without forming them; ``G`` passes a Gram already at hand."""
+    if init not in ("median", "mean"):
+        raise ValueError("init must be 'median' or 'mean'")
+    if _row_list(X) and not _gramfp_fused(X):
+        X = torch.stack(list(X))
+    fused = _gramfp_fused(X)
+    iters = int(fixed_iters) if fixed_iters is not None else int(max_iter)
+    tol = 0.0 if fixed_iters is not None else float(tol)
+    z0 = None
+    if init_z is not None:
+        z0 = init_z.detach()
+    elif init == "median" and mix is None:
+        if fused and not _row_list(X) and G is None and _median_gram_fused_ok(X):
+            z0, G = median_and_gram(X)
+        else:
+            z0 = median(X)
+    if G is None:
+        G = solver_gram(X)
+    W = None
+    if mix is not None:
+        G, W = mixed_gram(G, mix)
+    if z0 is None:
+        a = _live_uniform(G)
+    else:
+        if fused:
+            Xm = torch.stack(list(X)) if _row_list(X) else X.contiguous()
+            z0 = z0.to(device=Xm.device, dtype=torch.float32).contiguous()
+            s = _hip.require().row_center_sqdists(Xm, z0)
+        else:
+            s = ((X.double() - z0.to(X.device).double()[None, :]) ** 2).sum(dim=1)
+        w = 1.0 / s.double().sqrt().clamp(min=eps)
+        live = torch.isfinite(torch.diagonal(G)) & torch.isfinite(w)
+        w = torch.where(live, w, torch.zeros_like(w))
+        a = (w / w.sum()).to(G.dtype)
+        iters -= 1
+    a = gram_fixed_point(G, a, rule="weiszfeld", eps=eps, tol=tol, iters=iters)[0]
+    if W is not None:
+        a = W.T @ a.double()
+    return combine_rows(X, a)
+
+
+def mixed_geometric_median(
+    X: torch.Tensor,
+    mix: torch.Tensor,
+    *,
+    gram: Optional[torch.Tensor] = None,
+    tol: float = 1e-6,
+    max_iter: int = 256,
+    eps: float = 1e-12,
+    fixed_iters: Optional[int] = None,
+) -> torch.Tensor:
+    """The geometric median (solver="gram", mean init) of the mixed rows
+    (mix @ X) / mix.sum(1), with no mixed matrix: Gram, solver, combine — the
+    two passes over X of the unmixed rule. ``gram`` is X's Gram if the
+    caller already has it (NNM builds its membership from it)."""
+    return _geometric_median_gram(
+        X, tol=tol, max_iter=max_iter, eps=eps, init="mean",
+        fixed_iters=fixed_iters, init_z=None, mix=mix, G=gram,
+    )
+
+
+def _centered_clipping_gram(X, *, c_tau, M, eps, init) -> torch.Tensor:
+    if init not in ("mean", "zero"):
+        raise ValueError(
+            "solver='gram' needs init 'mean' or 'zero': from the median v "
+            "keeps a component outside the span of the rows"
+        )
+    if _row_list(X) and not _gramfp_fused(X):
+        X = torch.stack(list(X))
+    G = solver_gram(X)
+    a0 = _live_uniform(G) if init == "mean" else torch.zeros_like(G[0])
+    a = gram_fixed_point(G, a0, rule="cc", c_tau=c_tau, eps=eps, iters=M)[0]
+    return combine_rows(X, a)
+
+
 # -- iterative fixed-point ops (K6, K7) -------------------------------------
 
 
@@ -685,6 +886,7 @@ def geometric_median(
     init: str = "median",
     fixed_iters: Optional[int] = None,
     init_z: Optional[torch.Tensor] = None,
+    solver: str = "iterative",
 ) -> torch.Tensor:
     """Weiszfeld fixed point. ``fixed_iters`` runs exactly that many
     iterations with NO convergence polls — fully async (no host sync), so
@@ -692,7 +894,14 @@ def geometric_median(
     (the polls serialized config-4 gossip in round 1). ``init_z`` warm-
     starts from a caller-provided center (e.g. the previous gossip
     round's output — the fixed point barely moves between rounds, so a
-    handful of iterations replaces a cold median init + long descent)."""
+    handful of iterations replaces a cold median init + long descent).
+    ``solver="gram"`` runs the loop on the Gram instead (K20, above)."""
+    _check_solver(solver)
+    if solver == "gram":
+        return _geometric_median_gram(
+            X, tol=tol, max_iter=max_iter, eps=eps, init=init,
+            fixed_iters=fixed_iters, init_z=init_z,
+        )
     if not _gpu(X) or X.shape[0] > 1024:
         # extension's weiszfeld_iter TORCH_CHECKs n <= 1024; the torch
         # functional path runs fine on-device for larger n
@@ -829,7 +1038,11 @@ def centered_clipping(
     M: int = 10,
     eps: float = 1e-12,
     init: str = "mean",
+    solver: str = "iterative",
 ) -> torch.Tensor:
+    _check_solver(solver)
+    if solver == "gram":
+        return _centered_clipping_gram(X, c_tau=c_tau, M=M, eps=eps, init=init)
     if not _gpu(X) or X.shape[0] > 1024:
         # extension's cc_iter TORCH_CHECKs n <= 1024; fall back on-device
         return F.centered_clipping(X, c_tau=c_tau, M=M, eps=eps, init=init)

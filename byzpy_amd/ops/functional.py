@@ -375,6 +375,59 @@ def geometric_median(
     return z.to(X.dtype)
 
 
+def gram_fixed_point(
+    G: torch.Tensor,
+    a0: torch.Tensor,
+    *,
+    rule: str,
+    iters: int,
+    eps: float = 1e-12,
+    tol: float = 0.0,
+    c_tau: float = 0.0,
+):
+    """The Weiszfeld (``rule="weiszfeld"``) or centered-clipping
+    (``rule="cc"``) loop in coefficient space, in f64, on the Gram
+    G = X X^T: the iterate is z = a @ X, its distances are
+    d_i = max(sqrt(max(G_ii - 2 (G a)_i + a^T G a, 0)), eps) and a step
+    moves it by sqrt((a' - a)^T G (a' - a)). Weiszfeld: a' = w / sum w with
+    w = 1 / d, at most ``iters`` steps, stopping after the first one that
+    moved by <= tol (tol = 0 never stops early). Clipping:
+    a' = (1 - sum c / n) a + c / n with c = min(1, c_tau / d), exactly
+    ``iters`` steps. A row whose G_ii is not finite is dead: coefficient 0,
+    in no sum. Returns (a f64 (n,), steps, shift2 of the last step).
+
+    The oracle of the one-launch device solver (hip/csrc/gramfp.hip) and the
+    route of ``solver="gram"`` wherever that kernel does not apply."""
+    if rule not in ("weiszfeld", "cc"):
+        raise ValueError("rule must be 'weiszfeld' or 'cc'")
+    G = G.double()
+    n = G.shape[0]
+    live = torch.isfinite(torch.diagonal(G))
+    pair = live[:, None] & live[None, :] & torch.isfinite(G)
+    G = torch.where(pair, G, torch.zeros_like(G))
+    diag = torch.diagonal(G)
+    zero = torch.zeros(n, dtype=torch.float64, device=G.device)
+    a = torch.where(live, a0.double(), zero)
+    steps = 0
+    shift2 = torch.zeros((), dtype=torch.float64, device=G.device)
+    for _ in range(int(iters)):
+        u = G @ a
+        dist = (diag - 2.0 * u + a @ u).clamp(min=0.0).sqrt().clamp(min=eps)
+        if rule == "weiszfeld":
+            w = torch.where(live, 1.0 / dist, zero)
+            a_new = w / w.sum() if bool(live.any()) else zero
+        else:
+            c = torch.where(live, (c_tau / dist).clamp(max=1.0), zero)
+            a_new = (1.0 - c.sum() / n) * a + c / n
+        da = a_new - a
+        shift2 = da @ (G @ da)
+        a = a_new
+        steps += 1
+        if rule == "weiszfeld" and tol > 0.0 and float(shift2) <= tol * tol:
+            break
+    return a, steps, shift2
+
+
 def mda_subset(D2: torch.Tensor, f: int) -> Tuple[int, ...]:
     """Exact minimum-diameter (n-f)-subset search on a squared-distance
     matrix. Branch-and-bound DFS with prefix-max pruning — runs on the host

@@ -145,9 +145,14 @@ class NearestNeighborMixing(PreAggregator):
         """The (n, n) 0/1 matrix of the mixing, on X's device: row i marks
         the n - f nearest rows of row i (itself included), the indices
         ``_pre_aggregate`` averages."""
-        n = X.shape[0]
-        idx = D.nearest_rows_from_gram(D.gram(X), n - self.f)
-        mix = torch.zeros((n, n), dtype=torch.uint8, device=X.device)
+        return self.membership_from_gram(D.gram(X))
+
+    def membership_from_gram(self, G: torch.Tensor) -> torch.Tensor:
+        """``membership(X)`` from X's Gram, for a caller that needs the Gram
+        too and so spares a pass over X."""
+        n = G.shape[0]
+        idx = D.nearest_rows_from_gram(G, n - self.f)
+        mix = torch.zeros((n, n), dtype=torch.uint8, device=G.device)
         return mix.scatter_(1, idx, 1)
 
     def create_subtasks(self, ctx: OpContext, **inputs: Any) -> Sequence[SubTask]:
