@@ -158,17 +158,42 @@ class ComparativeGradientElimination(Aggregator):
 
 
 class CAF(Aggregator):
-    """Covariance-agnostic filter (power-iteration downweighting)."""
+    """Covariance-agnostic filter (power-iteration downweighting).
+
+    ``solver="gram"`` (opt-in) runs every round of the filter in coefficient
+    space on the Gram in one device launch: two passes over X however many
+    rounds run, no host sync, and device row lists read in place. It differs
+    from the iterative rule in two ways. (a) The start vector of each power
+    iteration is drawn in the span of the centred rows (n Gaussians), not in
+    R^d (d Gaussians): the same filter on a different random stream, so the
+    outputs agree with the iterative route only as far as the power iteration
+    has converged. (b) Projections come from an f32 Gram, so when the rows
+    share a mean much larger than their spread the centring cancels: a spread
+    below roughly 2^-11 of the rows' norm is not resolved. A row that holds
+    inf or NaN gets weight 0 and is left out."""
 
     name = "caf"
     supports_subtasks = False
 
-    def __init__(self, f: int, *, chunk_size: int = 256, power_iters: int = 3) -> None:
+    def __init__(
+        self,
+        f: int,
+        *,
+        chunk_size: int = 256,
+        power_iters: int = 3,
+        solver: str = "iterative",
+    ) -> None:
         if f < 0:
             raise ValueError("f must be >= 0")
+        if solver not in D.SOLVERS:
+            raise ValueError("solver must be 'iterative' or 'gram'")
+        self.solver = solver
+        if solver == "gram":
+            # device row lists are read where they are: no stacked copy
+            self._aggregate_rows = self._aggregate
         self.f = int(f)
         self.chunk_size = int(chunk_size)
         self.power_iters = int(power_iters)
 
     def _aggregate(self, X: torch.Tensor) -> torch.Tensor:
-        return D.caf(X, self.f, power_iters=self.power_iters)
+        return D.caf(X, self.f, power_iters=self.power_iters, solver=self.solver)

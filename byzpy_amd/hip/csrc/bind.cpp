@@ -1020,6 +1020,35 @@ torch::Tensor caf_matvec(torch::Tensor X, torch::Tensor mu, torch::Tensor v) {
   return out;
 }
 
+// caf_matvec(G, seeds, f=, power_iters=): the whole CAF filter loop in
+// coefficient space on the f32 Gram (gramfp.hip, K21), one launch. seeds is
+// (n, n) f32, row r the start vector of round r. Returns (a f32 (n,), lam f32
+// (), rounds int32 ()): the weights p of the round with the smallest
+// lambda, that lambda, and the rounds run. No host sync.
+std::vector<torch::Tensor> caf_gram(torch::Tensor G, torch::Tensor seeds,
+                                    int64_t f, int64_t power_iters) {
+  check_gram(G, "G");
+  const int64_t n = G.size(0);
+  TORCH_CHECK(n >= 1 && n <= GRAMFP_MAX_N, "caf_matvec(G, seeds) supports ",
+              "1 <= n <= ", GRAMFP_MAX_N, ", got ", n);
+  TORCH_CHECK(seeds.is_cuda() && seeds.scalar_type() == torch::kFloat32 &&
+                  seeds.is_contiguous() && seeds.dim() == 2 &&
+                  seeds.size(0) == n && seeds.size(1) == n,
+              "seeds: expected an f32 contiguous device matrix (", n, ", ", n,
+              ")");
+  TORCH_CHECK(seeds.device() == G.device(), "seeds: expected G's device");
+  TORCH_CHECK(f >= 0 && n - 2 * f > 0, "caf_matvec(G, seeds) needs f >= 0 and ",
+              "n - 2f > 0, got n=", n, ", f=", f);
+  TORCH_CHECK(power_iters >= INT_MIN && power_iters <= INT_MAX,
+              "power_iters: out of range");
+  auto a = torch::empty({n}, f32_like(G));
+  auto lam = torch::empty({}, f32_like(G));
+  auto rounds = torch::empty({}, i32_like(G));
+  launch_caf_gram(f32(G), f32(seeds), (int)n, (int)f, (int)power_iters, f32(a),
+                  f32(lam), i32(rounds), cur_stream());
+  return {a, lam, rounds};
+}
+
 torch::Tensor caf_colsum(torch::Tensor X, torch::Tensor a,
                          c10::optional<torch::Tensor> mu,
                          c10::optional<torch::Tensor> scale) {
@@ -1095,6 +1124,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("G"), py::arg("f"), py::arg("q"), py::kw_only(),
         py::arg("stats"), py::arg("rule"), py::arg("gammas") = c10::nullopt);
   m.def("caf_matvec", &caf_matvec);
+  m.def("caf_matvec", &caf_gram,
+        "the CAF filter loop on the Gram (K21): (a, lam, rounds)",
+        py::arg("G"), py::arg("seeds"), py::kw_only(), py::arg("f"),
+        py::arg("power_iters"));
   m.def("caf_colsum", &caf_colsum, py::arg("X"), py::arg("a"),
         py::arg("mu") = c10::nullopt, py::arg("scale") = c10::nullopt);
   m.def("weiszfeld_iter", &weiszfeld_iter);

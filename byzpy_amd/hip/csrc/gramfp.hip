@@ -35,12 +35,13 @@ constexpr int GFP_THREADS = 1024;
 constexpr int GFP_SEG = 16;  // Gram entries of one row per thread
 constexpr int GFP_MAX_SEGS = GRAMFP_MAX_N / GFP_SEG;
 static_assert(GFP_MAX_SEGS * GRAMFP_MAX_N <= GFP_THREADS, "one thread per (segment, row)");
+constexpr int GFP_MAX_SUMS = 4;  // vectors one two-level sum reduces at once
 
 struct GfpShared {
   double part[GFP_MAX_SEGS][GRAMFP_MAX_N];  // segment partials of the matvec
   double x[GRAMFP_MAX_N];                   // the matvec's operand, 0 past n
-  double v[2][GRAMFP_MAX_N];                // two vectors to be summed, 0 past n
-  double seg[2][GFP_MAX_SEGS];              // their segment sums
+  double v[GFP_MAX_SUMS][GRAMFP_MAX_N];     // vectors to be summed, 0 past n
+  double seg[GFP_MAX_SUMS][GFP_MAX_SEGS];   // their segment sums
 };
 
 // Which part of the block a thread is: (r, i) of the matvec, a row owner
@@ -69,26 +70,69 @@ DEV double gfp_matvec(GfpShared& s, const GfpThread& t,
   return y;
 }
 
-// s0 = sum s.v[0], s1 = sum s.v[1], the same in every thread. s.v must have
+// out[j] = sum s.v[j] for j < K, the same in every thread; with MAXLAST the
+// last one is the maximum of s.v[K - 1] instead (values >= 0). s.v must have
 // been written by the slot threads; the leading barrier publishes it.
-DEV void gfp_sum2(GfpShared& s, const GfpThread& t, double& s0, double& s1) {
+template <int K, bool MAXLAST = false>
+DEV void gfp_sum(GfpShared& s, const GfpThread& t, double (&out)[K]) {
+  static_assert(K <= GFP_MAX_SUMS, "one LDS vector per sum");
   __syncthreads();
   if (t.tid < t.segs) {
-    double t0 = 0.0, t1 = 0.0;
+    double acc[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) acc[j] = 0.0;
 #pragma unroll
     for (int k = 0; k < GFP_SEG; ++k) {
-      t0 += s.v[0][t.tid * GFP_SEG + k];
-      t1 += s.v[1][t.tid * GFP_SEG + k];
+#pragma unroll
+      for (int j = 0; j < K; ++j) {
+        const double x = s.v[j][t.tid * GFP_SEG + k];
+        acc[j] = (MAXLAST && j == K - 1) ? fmax(acc[j], x) : acc[j] + x;
+      }
     }
-    s.seg[0][t.tid] = t0;
-    s.seg[1][t.tid] = t1;
+#pragma unroll
+    for (int j = 0; j < K; ++j) s.seg[j][t.tid] = acc[j];
   }
   __syncthreads();
-  s0 = 0.0;
-  s1 = 0.0;
-  for (int k = 0; k < t.segs; ++k) {
-    s0 += s.seg[0][k];
-    s1 += s.seg[1][k];
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    double r = 0.0;
+    for (int k = 0; k < t.segs; ++k) {
+      const double x = s.seg[j][k];
+      r = (MAXLAST && j == K - 1) ? fmax(r, x) : r + x;
+    }
+    out[j] = r;
+  }
+}
+
+DEV void gfp_sum2(GfpShared& s, const GfpThread& t, double& s0, double& s1) {
+  double r[2];
+  gfp_sum<2>(s, t, r);
+  s0 = r[0];
+  s1 = r[1];
+}
+
+// Which part of the block this thread is, for n rows.
+DEV GfpThread gfp_thread(int n) {
+  GfpThread t;
+  t.tid = threadIdx.x;
+  t.segs = (n + GFP_SEG - 1) / GFP_SEG;
+  t.i = t.tid % n;
+  t.r = t.tid / n;
+  t.active = t.r < t.segs;
+  t.row = t.tid < n;
+  t.slot = t.tid < GRAMFP_MAX_N;
+  return t;
+}
+
+// Thread (r, i)'s 16 Gram entries; entries that are not finite are read as 0.
+DEV void gfp_load(const float* __restrict__ G, int n, const GfpThread& t,
+                  float (&g)[GFP_SEG]) {
+#pragma unroll
+  for (int m = 0; m < GFP_SEG; ++m) {
+    const int k = t.r * GFP_SEG + m;
+    float x = (t.active && k < n) ? G[(long)t.i * n + k] : 0.0f;
+    if (!(fabsf(x) < INFINITY)) x = 0.0f;
+    g[m] = x;
   }
 }
 
@@ -100,23 +144,9 @@ gram_fixed_point_kernel(const float* __restrict__ G,
                         float* __restrict__ a_out, int* __restrict__ steps_out,
                         float* __restrict__ shift2_out) {
   __shared__ GfpShared s;
-  GfpThread t;
-  t.tid = threadIdx.x;
-  t.segs = (n + GFP_SEG - 1) / GFP_SEG;
-  t.i = t.tid % n;
-  t.r = t.tid / n;
-  t.active = t.r < t.segs;
-  t.row = t.tid < n;
-  t.slot = t.tid < GRAMFP_MAX_N;
-
+  const GfpThread t = gfp_thread(n);
   float g[GFP_SEG];
-#pragma unroll
-  for (int m = 0; m < GFP_SEG; ++m) {
-    const int k = t.r * GFP_SEG + m;
-    float x = (t.active && k < n) ? G[(long)t.i * n + k] : 0.0f;
-    if (!(fabsf(x) < INFINITY)) x = 0.0f;
-    g[m] = x;
-  }
+  gfp_load(G, n, t, g);
   // row scalars; all 0 in the threads that own no live row
   double gii = 0.0, a = 0.0;
   bool live = false;
@@ -176,6 +206,136 @@ gram_fixed_point_kernel(const float* __restrict__ G,
   }
 }
 
+// -- CAF on the Gram (K21) ----------------------------------------------------
+//
+// The covariance-bound filter never leaves the span of the centred rows. With
+// weights w, p = w / sum w, mu = X^T p, y_i = x_i - mu and a direction
+// v = Y^T b, the weighted covariance acts on the n coefficients as
+//   C b = H G H^T b,  H = I - 1 p^T:
+//   bt = b - p sum(b),  u = G bt,  (C b)_i = u_i - p.u,  p.u = (G p).bt.
+// s = C b are the projections Y v, a power step is b' = p o s with
+// ||Y^T b'||^2 = b'^T C b', and the downweighting, the stop test and the
+// best-lambda tracking need s, w and lambda only. So the whole filter, all
+// its rounds, is this one block on the register-resident Gram.
+//
+// What a round costs is block-wide barriers, 2 per matvec and 2 per two-level
+// sum, so the loop is laid out to need few of them:
+//  - G p is one matvec per round. With it, p.u = (G p).b - ((G p).p) sum(b):
+//    the centring scalar sum(b) and (G p).b ride in ONE sum, taken BEFORE the
+//    matvec, and the centring itself is folded into the operand bt.
+//  - A power step is one matvec and one sum. The sum that follows the matvec
+//    returns the quadratic form b'^T C b', and already sum(b'') and
+//    (G p).b'' of the next step's b'' = p o s' (scaled by 1 / lambda
+//    afterwards, C being linear), and max |s'| for the downweighting. The
+//    C b' that gives lambda is, over lambda, the next step's s: no matvec is
+//    spent on projections.
+//  Barriers: 4 per power step; per round 2 (G p) + 2 (seed sums) + 2 (C seed)
+//  + 2 (its norm) + 4 * steps + 2 (sum w_next) = 10 + 4 * steps, 22 at the
+//  default 3 steps. There are at most n rounds.
+// The loop ends on a block-wide vote: every thread holds the same wsum and
+// sum(w_next). The next round's wsum IS this round's sum(w_next).
+//
+// Everything past the f32 Gram entries is f64, every sum runs in index order
+// and there are no atomics: the same bits in give the same bits out. Every
+// quadratic form is clamped at 0 before its square root (an f32-rounded Gram
+// is not exactly PSD). Dead rows (G_ii not finite) have w = 0 from the start,
+// seed entry 0, projection 0, and enter no sum and no maximum.
+//
+// Measured on MI355X (benchmarks/RESULTS_MI355X_caf_gram.md): a round takes
+// about 10 us at n = 64 and 16 us at n = 128. A typical launch (2 rounds) is
+// 0.02 to 0.04 ms, 6 % of one pass over a 64 x 16M bf16 matrix (0.37 ms). The
+// worst case, all n rounds, is 0.63 ms at n = 64 and 2.03 ms at n = 128: MORE
+// than one pass over X, five of them at n = 128.
+__global__ void __launch_bounds__(GFP_THREADS)
+caf_gram_kernel(const float* __restrict__ G, const float* __restrict__ seeds,
+                int n, int f, int steps, float* __restrict__ a_out,
+                float* __restrict__ lam_out, int* __restrict__ rounds_out) {
+  __shared__ GfpShared s;
+  const GfpThread t = gfp_thread(n);
+  float g[GFP_SEG];
+  gfp_load(G, n, t, g);
+  const bool live = t.row && fabsf(G[(long)t.tid * n + t.tid]) < INFINITY;
+
+  double w = live ? 1.0 : 0.0;
+  double r1[1], r3[3], r4[4];
+  if (t.slot) s.v[0][t.tid] = w;
+  gfp_sum<1>(s, t, r1);
+  double wsum = r1[0];  // the number of live rows
+  const double target = (double)(n - 2 * f);
+  double best = wsum > 0.0 ? w / wsum : 0.0;
+  double best_lambda = INFINITY;
+  int rounds = 0;
+
+  // wsum > 0 at the top of every round: a round whose sum(w_next) is 0 stops
+  for (int r = 0; r < n && wsum > 0.0; ++r) {
+    const double p = w / wsum;
+    if (t.slot) s.x[t.tid] = p;
+    const double gp = gfp_matvec(s, t, g);  // 0 in dead rows: p is 0 there
+    const double b = live ? (double)seeds[(long)r * n + t.tid] : 0.0;
+    if (t.slot) {
+      s.v[0][t.tid] = b;
+      s.v[1][t.tid] = gp * b;
+      s.v[2][t.tid] = gp * p;
+    }
+    gfp_sum<3>(s, t, r3);
+    const double gpp = r3[2];
+    // sc = s / nrm is C of the unit-length seed direction
+    if (t.slot) s.x[t.tid] = b - p * r3[0];
+    double sc = gfp_matvec(s, t, g);
+    sc = live ? sc - (r3[1] - gpp * r3[0]) : 0.0;
+    if (t.slot) {
+      s.v[0][t.tid] = b * sc;
+      s.v[1][t.tid] = p * sc;
+      s.v[2][t.tid] = gp * p * sc;
+    }
+    gfp_sum<3>(s, t, r3);
+    double scale = fmax(sqrt(fmax(r3[0], 0.0)), 1e-20);
+    sc /= scale;
+    double sb = r3[1] / scale;  // sum(b') and (G p).b' of b' = p o sc
+    double gb = r3[2] / scale;
+    double lambda = 0.0, smax = 0.0;
+    for (int k = 0; k < steps; ++k) {
+      const double bp = p * sc;
+      if (t.slot) s.x[t.tid] = bp - p * sb;
+      double sn = gfp_matvec(s, t, g);
+      sn = live ? sn - (gb - gpp * sb) : 0.0;
+      if (t.slot) {
+        s.v[0][t.tid] = bp * sn;
+        s.v[1][t.tid] = p * sn;
+        s.v[2][t.tid] = gp * p * sn;
+        s.v[3][t.tid] = fabs(sn);
+      }
+      gfp_sum<4, true>(s, t, r4);
+      lambda = sqrt(fmax(r4[0], 0.0));
+      scale = fmax(lambda, 1e-20);
+      sc = sn / scale;
+      sb = r4[1] / scale;
+      gb = r4[2] / scale;
+      smax = r4[3] / scale;
+    }
+    if (lambda < best_lambda) {  // strict: the first minimum wins
+      best_lambda = lambda;
+      best = p;
+    }
+    // max_i (sc_i^2) == (max_i |sc_i|)^2 bit for bit: rounding is monotone
+    const double pmax = fmax(smax * smax, 1e-20);
+    const double wn = fmax(w * (1.0 - sc * sc / pmax), 0.0);
+    if (t.slot) s.v[0][t.tid] = wn;
+    gfp_sum<1>(s, t, r1);
+    ++rounds;
+    // every thread holds the same wsum and r1[0]: the vote is unanimous
+    if (wsum <= target || r1[0] <= 0.0) break;
+    w = wn;
+    wsum = r1[0];
+  }
+
+  if (t.row) a_out[t.tid] = (float)best;
+  if (t.tid == 0) {
+    *lam_out = (float)best_lambda;
+    *rounds_out = rounds;
+  }
+}
+
 }  // namespace
 
 void launch_gram_fixed_point(const float* G, const float* a0, int n, int rule,
@@ -195,4 +355,15 @@ void launch_gram_fixed_point(const float* G, const float* a0, int n, int rule,
     hipLaunchKernelGGL(gram_fixed_point_kernel<false>, dim3(1), dim3(threads),
                        0, stream, G, a0, n, eps, tol2, c_tau, iters, a, steps,
                        shift2);
+}
+
+void launch_caf_gram(const float* G, const float* seeds, int n, int f,
+                     int power_iters, float* a, float* lam, int* rounds,
+                     hipStream_t stream) {
+  const int segs = (n + GFP_SEG - 1) / GFP_SEG;
+  int threads = ((segs * n + 63) / 64) * 64;
+  if (threads < GRAMFP_MAX_N) threads = GRAMFP_MAX_N;
+  const int steps = power_iters < 1 ? 1 : power_iters;
+  hipLaunchKernelGGL(caf_gram_kernel, dim3(1), dim3(threads), 0, stream, G,
+                     seeds, n, f, steps, a, lam, rounds);
 }

@@ -140,6 +140,21 @@ void launch_gram_fixed_point(const float* G, const float* a0, int n, int rule,
                              double eps, double tol2, double c_tau, int iters,
                              float* a, int* steps, float* shift2,
                              hipStream_t stream);
+// gramfp.hip (K21): the whole CAF filter loop on the f32 Gram G (n, n), one
+// workgroup, one launch. seeds is (n, n) f32: row r is the start of round r's
+// power iteration, as coefficients over the centred rows. Per round: p = w /
+// sum w; max(1, power_iters) power steps on C = H G H^T, H = I - 1 p^T, from
+// the seed scaled to a unit direction; lambda = the last step's norm; the
+// round with the smallest lambda (the first, on a tie) leaves its p as the
+// answer; w <- max(w (1 - proj / max proj), 0) with proj the squared
+// projections; the loop ends after the round with sum w <= n - 2f or
+// sum w_next <= 0, or after n rounds. A row whose G_ii is not finite is dead:
+// w = 0 from the start, in no sum. f64 past the f32 entries, fixed order:
+// bitwise repeatable. Writes a (n,) f32 (the best p), its lambda and the
+// number of rounds run. 1 <= n <= GRAMFP_MAX_N, n - 2f > 0. No host sync.
+void launch_caf_gram(const float* G, const float* seeds, int n, int f,
+                     int power_iters, float* a, float* lam, int* rounds,
+                     hipStream_t stream);
 // rowptrs.hip (K20): out = sum_i coef[i] x_i, not normalised, f32 accumulation
 // in row order, out in T. Rows with coef[i] == 0 are never read. X null: the
 // rows are the table's (n <= ROWPTR_MAX_N); else rows of the contiguous (n, d)

@@ -1827,17 +1827,71 @@ def _caf_graph_ok(X: torch.Tensor, f: int) -> bool:
     return n <= 256 and d <= _CAF_GRAPH_MAX_D
 
 
-def caf(X: torch.Tensor, f: int, *, power_iters: int = 3) -> torch.Tensor:
+# -- CAF on the Gram (K21) ------------------------------------------------------
+#
+# ``solver="gram"`` of caf. Every quantity of the filter loop lives in the
+# span of the centred rows (F.caf_gram), so the loop runs on the (n, n) Gram
+# in one launch (caf_gram_kernel, csrc/gramfp.hip) between the two passes over
+# X of K20: the MFMA Gram and ``mean_rows(X, coeffs=)``. No host sync, no
+# d-long random vectors, device row lists read in place. Opt-in: the power
+# iteration starts in the row span (n Gaussians per round, not d), so it is
+# the same filter on another random stream, and the projections come from an
+# f32 Gram.
+
+_CAF_GRAM_SEEDS: dict = {}
+_CAF_GRAM_SEEDS_MAX = 8  # FIFO cap: an entry is at most 64 KB
+
+
+def _caf_gram_device_seeds(n: int, device) -> torch.Tensor:
+    key = (n, device.type, device.index)
+    seeds = _CAF_GRAM_SEEDS.get(key)
+    if seeds is None:
+        if len(_CAF_GRAM_SEEDS) >= _CAF_GRAM_SEEDS_MAX:
+            _CAF_GRAM_SEEDS.pop(next(iter(_CAF_GRAM_SEEDS)))
+        seeds = F.caf_gram_seeds(n).to(device)
+        _CAF_GRAM_SEEDS[key] = seeds
+    return seeds
+
+
+def caf_gram(G: torch.Tensor, f: int, *, power_iters: int = 3):
+    """(a, lam, rounds) of F.caf_gram on the seeds F.caf_gram_seeds(n): one
+    launch and no host sync for an f32 device Gram of n <= GRAMFP_MAX_N rows
+    (lam and rounds stay device scalars), the f64 torch loop otherwise."""
+    n = G.shape[0]
+    if n - 2 * f <= 0:
+        raise ValueError(f"need n - 2f > 0, got n={n}, f={f}")
+    if _gpu(G) and G.dtype == torch.float32 and 1 <= n <= GRAMFP_MAX_N:
+        return tuple(_hip.require().caf_matvec(
+            G.contiguous(), _caf_gram_device_seeds(n, G.device),
+            f=int(f), power_iters=int(power_iters),
+        ))
+    return F.caf_gram(G, f, F.caf_gram_seeds(n), power_iters=power_iters)
+
+
+def _caf_on_gram(X, f: int, power_iters: int) -> torch.Tensor:
+    if _row_list(X) and not _gramfp_fused(X):
+        X = torch.stack(list(X))
+    a = caf_gram(solver_gram(X), f, power_iters=power_iters)[0]
+    return combine_rows(X, a)
+
+
+def caf(
+    X: torch.Tensor, f: int, *, power_iters: int = 3, solver: str = "iterative"
+) -> torch.Tensor:
     """Covariance-agnostic filter on fused K9 kernels (reference
     caf.py:133-184): caf_matvec computes s = (X - mu) @ v, caf_colsum
     computes weighted centered column sums — neither materializes the
     (n, d) f32 diffs matrix and both replace rocblas gemvt (~260 GB/s on
     this skinny shape). Same algorithm and seeded-rng contract as the
     functional oracle. Steady-state shapes run the hipGraph block path
-    (_CafGraphBlock); others fall back to the eager loop below."""
+    (_CafGraphBlock); others fall back to the eager loop below.
+    ``solver="gram"`` runs the loop on the Gram instead (K21, above)."""
     import math
     import os
 
+    _check_solver(solver)
+    if solver == "gram":
+        return _caf_on_gram(X, int(f), int(power_iters))
     n = X.shape[0]
     if not (_gpu(X) and n <= 1024 and n - 2 * f > 0):
         return F.caf(X, f, power_iters=power_iters)

@@ -668,6 +668,90 @@ def caf(X: torch.Tensor, f: int, *, power_iters: int = 3) -> torch.Tensor:
     return best_mu.to(X.dtype)
 
 
+def caf_gram_seeds(n: int) -> torch.Tensor:
+    """The (n, n) f32 seed matrix of ``caf_gram``: row r is the start of round
+    r's power iteration, as coefficients over the centred rows. Seeded CPU
+    rng, so it depends on n alone."""
+    gen = torch.Generator(device="cpu")
+    gen.manual_seed(0)
+    return torch.randn(n, n, generator=gen)
+
+
+def caf_gram(
+    G: torch.Tensor,
+    f: int,
+    seeds: torch.Tensor,
+    *,
+    power_iters: int = 3,
+    trace: bool = False,
+):
+    """The CAF loop of ``caf`` in coefficient space, in f64, on the Gram
+    G = X X^T. With weights w, p = w / sum w and centred rows y_i = x_i - p @ X,
+    a direction v = b @ Y has projections Y v = C b, C = H G H^T, H = I - 1 p^T:
+    bt = b - p sum(b), u = G bt, (C b)_i = u_i - (G p).bt. A power step is
+    b' = p o (C b) with ||b' @ Y||^2 = b'^T C b'. Round r starts from
+    b = seeds[r] scaled to a unit direction (``caf`` draws its start in R^d:
+    the one difference); everything else follows ``caf`` round for round.
+    Quadratic forms are clamped at 0 before their square root. A row whose
+    G_ii is not finite is dead: w = 0 from the start, in no sum.
+
+    Returns (a f64 (n,), lam, rounds): the p of the round with the smallest
+    lambda (the first, on a tie), so the answer is a @ X, that lambda and the
+    rounds run. ``trace=True`` appends the per-round lists of lambda, sum(w)
+    and sum(w_next).
+
+    The oracle of the one-launch device solver (hip/csrc/gramfp.hip) and the
+    route of ``CAF(solver="gram")`` wherever that kernel does not apply."""
+    G = G.double()
+    n = G.shape[0]
+    if n - 2 * f <= 0:
+        raise ValueError(f"need n - 2f > 0, got n={n}, f={f}")
+    live = torch.isfinite(torch.diagonal(G))
+    pair = live[:, None] & live[None, :] & torch.isfinite(G)
+    G = torch.where(pair, G, torch.zeros_like(G))
+    zero = torch.zeros(n, dtype=torch.float64, device=G.device)
+    seeds = seeds.to(device=G.device, dtype=torch.float64)
+    w = live.double()
+    wsum = w.sum()
+    best = w / wsum.clamp(min=1.0)
+    best_lambda = math.inf
+    target = float(n - 2 * f)
+    lams, wsums, wnexts = [], [], []
+    for r in range(n if bool(live.any()) else 0):
+        p = w / wsum
+        gp = G @ p
+        gpp = gp @ p
+
+        def cov(b):
+            sb = b.sum()
+            u = G @ (b - p * sb)
+            return torch.where(live, u - (gp @ b - gpp * sb), zero)
+
+        b = torch.where(live, seeds[r], zero)
+        s = cov(b)
+        s = s / max(math.sqrt(max(float(b @ s), 0.0)), 1e-20)
+        lam = 0.0
+        for _ in range(max(1, power_iters)):
+            b = p * s
+            s = cov(b)
+            lam = math.sqrt(max(float(b @ s), 0.0))
+            s = s / max(lam, 1e-20)
+        if lam < best_lambda:
+            best_lambda, best = lam, p
+        proj = s * s
+        pmax = max(float(proj.max()), 1e-20)
+        w_next = (w * (1.0 - proj / pmax)).clamp(min=0.0)
+        wnext_sum = w_next.sum()
+        lams.append(lam)
+        wsums.append(float(wsum))
+        wnexts.append(float(wnext_sum))
+        if float(wsum) <= target or float(wnext_sum) <= 0.0:
+            break
+        w, wsum = w_next, wnext_sum
+    out = (best, best_lambda, len(lams))
+    return out + (lams, wsums, wnexts) if trace else out
+
+
 # ---------------------------------------------------------------------------
 # pre-aggregators (list -> list semantics; matrix in, matrix out here)
 # ---------------------------------------------------------------------------
