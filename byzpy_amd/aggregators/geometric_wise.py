@@ -26,20 +26,33 @@ from byzpy_amd.utils.flatten import stack_gradients, to_like
 
 class MultiKrum(Aggregator):
     """Pairwise sq-dists -> score_i = sum of n-f-1 nearest -> mean of the q
-    best (Blanchard et al. 2017). Row-chunked Gram on CPU pools."""
+    best (Blanchard et al. 2017). Row-chunked Gram on CPU pools.
+
+    ``centered=True`` takes the distances from the column-centred Gram
+    (``D.gram(X, center=True)``, K22): rows that share a large component,
+    such as parameter vectors or momenta, are told apart by their true
+    distances instead of f32 cancellation noise; see D.gram for the accuracy
+    model. Device gradients are then stacked, not read in place. The CPU
+    pool's chunked path ignores the flag (it builds the raw row-chunk
+    Gram)."""
 
     name = "multi-krum"
     supports_subtasks = True
     max_subtasks_inflight = 0
 
-    def __init__(self, f: int, q: int, *, chunk_size: int = 32) -> None:
+    def __init__(
+        self, f: int, q: int, *, chunk_size: int = 32, centered: bool = False
+    ) -> None:
         if f < 0 or q < 1:
             raise ValueError("need f >= 0 and q >= 1")
         self.f, self.q = int(f), int(q)
         self.chunk_size = int(chunk_size)
+        self.centered = bool(centered)
+        if self.centered:
+            self._aggregate_rows = None  # the centred Gram takes a matrix
 
     def _aggregate(self, X: torch.Tensor) -> torch.Tensor:
-        return D.multi_krum(X, self.f, self.q)
+        return D.multi_krum(X, self.f, self.q, centered=self.centered)
 
     def _aggregate_rows(self, rows: List[torch.Tensor]) -> torch.Tensor:
         return D.multi_krum(rows, self.f, self.q)
@@ -72,11 +85,13 @@ class Krum(MultiKrum):
 
     name = "krum"
 
-    def __init__(self, f: int, *, chunk_size: int = 32) -> None:
-        super().__init__(f, 1, chunk_size=chunk_size)
+    def __init__(
+        self, f: int, *, chunk_size: int = 32, centered: bool = False
+    ) -> None:
+        super().__init__(f, 1, chunk_size=chunk_size, centered=centered)
 
     def _aggregate(self, X: torch.Tensor) -> torch.Tensor:
-        return D.krum(X, self.f)
+        return D.krum(X, self.f, centered=self.centered)
 
     def _aggregate_rows(self, rows: List[torch.Tensor]) -> torch.Tensor:
         return D.krum(rows, self.f)
@@ -95,17 +110,21 @@ class Bulyan(Aggregator):
     iterated Krum, then per coordinate the mean of the n - 4f selected
     values closest to their median. Needs n >= 4f + 3. Row-chunked Gram on
     CPU pools; Gram + one selection launch + one indexed column launch on
-    GPU."""
+    GPU. ``centered=True``: the picks come from the column-centred Gram, as
+    in MultiKrum; the CPU pool's chunked path ignores the flag."""
 
     name = "bulyan"
     supports_subtasks = True
     max_subtasks_inflight = 0
 
-    def __init__(self, f: int, *, chunk_size: int = 32) -> None:
+    def __init__(
+        self, f: int, *, chunk_size: int = 32, centered: bool = False
+    ) -> None:
         if f < 0:
             raise ValueError("f must be >= 0")
         self.f = int(f)
         self.chunk_size = int(chunk_size)
+        self.centered = bool(centered)
 
     def _check(self, n: int) -> None:
         if n < 4 * self.f + 3:
@@ -115,7 +134,7 @@ class Bulyan(Aggregator):
 
     def _aggregate(self, X: torch.Tensor) -> torch.Tensor:
         self._check(X.shape[0])
-        return D.bulyan(X, self.f)
+        return D.bulyan(X, self.f, centered=self.centered)
 
     def create_subtasks(self, ctx: OpContext, **inputs: Any) -> Sequence[SubTask]:
         gradients = inputs[self.input_key]
@@ -415,7 +434,14 @@ class GeometricMedian(Aggregator):
     closer to the centre than roughly 2^-11 of its own norm is not resolved
     and its weight saturates at that floor, not at ``eps``. A row that holds
     inf or NaN gets weight 0 and is left out. The CPU pool fan-out is the
-    iterative rule under either solver."""
+    iterative rule under either solver.
+
+    ``centered=True`` (with ``solver="gram"`` and ``init="mean"`` only) runs
+    the solver on the column-centred Gram (K22): exact, because the
+    coefficients sum to 1 at every step, and the limit above becomes 2^-11
+    of the row's distance from the column mean (bf16 input: 2^-9 of it, the
+    one rounding of x - mu). The rows are stacked, not read in place. The
+    CPU pool fan-out takes differences and ignores the flag."""
 
     name = "geometric-median"
     supports_barriered_subtasks = True
@@ -431,6 +457,7 @@ class GeometricMedian(Aggregator):
         chunk_size: int = 32,
         fixed_iters: "int | None" = None,
         solver: str = "iterative",
+        centered: bool = False,
     ) -> None:
         if tol <= 0 or max_iter <= 0 or eps <= 0:
             raise ValueError("tol, max_iter, eps must be > 0")
@@ -438,8 +465,11 @@ class GeometricMedian(Aggregator):
             raise ValueError("init must be 'median' or 'mean'")
         if solver not in D.SOLVERS:
             raise ValueError("solver must be 'iterative' or 'gram'")
+        if centered and (solver != "gram" or init != "mean"):
+            raise ValueError("centered=True needs solver='gram' and init='mean'")
         self.solver = solver
-        if solver == "gram" and init == "mean":
+        self.centered = bool(centered)
+        if solver == "gram" and init == "mean" and not centered:
             # device row lists are read where they are: no stacked copy
             self._aggregate_rows = self._aggregate
         if fixed_iters is not None and fixed_iters <= 0:
@@ -456,7 +486,8 @@ class GeometricMedian(Aggregator):
     def _aggregate(self, X: torch.Tensor) -> torch.Tensor:
         return D.geometric_median(
             X, tol=self.tol, max_iter=self.max_iter, eps=self.eps,
-            init=self.init, fixed_iters=self.fixed_iters, solver=self.solver
+            init=self.init, fixed_iters=self.fixed_iters, solver=self.solver,
+            centered=self.centered,
         )
 
     async def run_barriered_subtasks(self, ctx: OpContext, **inputs: Any) -> Any:

@@ -29,7 +29,8 @@ class PreAggregated(Aggregator):
     takes the fused device route where ``D.mixed_colsel_fused_ok(X)``; in
     front of ``GeometricMedian(solver="gram", init="mean")`` the rule runs on
     the mixed Gram W G W^T and the coefficients pull back as W^T a, so no
-    mixed matrix is formed on any device; everything else is
+    mixed matrix is formed on any device (``centered=True`` on either part
+    puts that route on the column-centred Gram); everything else is
     ``aggregator._aggregate(pre_aggregator._pre_aggregate(X))``."""
 
     name = "pre-aggregated"
@@ -53,8 +54,13 @@ class PreAggregated(Aggregator):
             and agg.init == "mean"
         ):
             # Gram of Y = W X is W G W^T and coefficients pull back as W^T a:
-            # the rule runs on the mixed rows with no mixed matrix (K20)
-            G = D.solver_gram(X)
+            # the rule runs on the mixed rows with no mixed matrix (K20).
+            # ``centered=True`` on either part takes the centred Gram (K22)
+            # for both: W's rows and the Weiszfeld coefficients sum to 1, so
+            # W Gc W^T is the Gram of the mixed rows less the same mu, with
+            # the same distances, and W^T a still combines the raw rows.
+            centered = getattr(pre, "centered", False) or agg.centered
+            G = D.solver_gram(X, centered)
             if hasattr(pre, "membership_from_gram"):
                 mix = pre.membership_from_gram(G)
             else:

@@ -20,7 +20,7 @@ OUT_SO = PKG_DIR / "_hip_ops.so"
 BUILD_DIR = PKG_DIR.parent / "build" / "hip"
 
 SOURCES = ["colsel.hip", "colsel_mix.hip", "rsel.hip", "rowops.hip", "gram.hip",
-           "rowptrs.hip", "krumsel.hip", "subsets.hip", "gramfp.hip", "attacks.hip",
+           "gram_centered.hip", "rowptrs.hip", "krumsel.hip", "subsets.hip", "gramfp.hip", "attacks.hip",
            "mda_host.cpp", "bind.cpp"]
 HEADERS = ["common.h", "launchers.h", "mda_host.h", "oem_sort.h", "selnet.h",
            "colsel_shared.h"]
@@ -28,11 +28,15 @@ HEADERS = ["common.h", "launchers.h", "mda_host.h", "oem_sort.h", "selnet.h",
 # Per-file flags. colsel_mix.hip keeps its f32 scaling and summing on the
 # one-value-per-lane VALU forms: built without v_pk_add/mul/fma_f32; so does
 # rowptrs.hip (the row means and the coefficient combine) and gramfp.hip.
+# gram_centered.hip follows them for its column sums and x - mu: every file
+# added since colsel_mix.hip that sums in f32 is built this way, and its f32
+# VALU work (two adds and two subtracts per LDS word) is not what bounds it.
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
     "colsel_mix.hip": _NO_PK_F32,
     "rowptrs.hip": _NO_PK_F32,
     "gramfp.hip": _NO_PK_F32,
+    "gram_centered.hip": _NO_PK_F32,
 }
 
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")

@@ -437,14 +437,24 @@ torch::Tensor bucket_mean(torch::Tensor X, torch::Tensor perm,
   return out;
 }
 
-torch::Tensor gram(torch::Tensor X) {
+// gram(X): X X^T. gram(X, center=True): the column-centred Gram of
+// gram_centered.hip (K22), n <= GRAM_CENTERED_MAX_N.
+torch::Tensor gram(torch::Tensor X, bool center) {
   check_matrix(X);
+  TORCH_CHECK(!center || (X.size(0) >= 1 && X.size(0) <= GRAM_CENTERED_MAX_N),
+              "gram(center=True) supports 1 <= n <= ", GRAM_CENTERED_MAX_N,
+              ", got ", X.size(0));
+  TORCH_CHECK(!center || X.size(1) >= 1,
+              "gram(center=True) needs at least one column");
   const int n = (int)X.size(0);
   const long d = (long)X.size(1);
   auto G = torch::zeros({n, n}, f32_like(X));
   by_dtype(X, [&](auto tag) {
     using T = TAG_T(tag);
-    launch_gram<T>(ptr<T>(X), f32(G), n, d, cur_stream());
+    if (center)
+      launch_gram_centered<T>(ptr<T>(X), f32(G), n, d, cur_stream());
+    else
+      launch_gram<T>(ptr<T>(X), f32(G), n, d, cur_stream());
   });
   return G;
 }
@@ -452,7 +462,10 @@ torch::Tensor gram(torch::Tensor X) {
 // gram(X, cols=c): the sampled centred Grams of DnC (gram.hip). cols is an
 // int32 (niters, b) device tensor of column indices (clamped to [0, d));
 // returns (Gc f32 (niters, n, n), bad int32 (niters, n)). Bitwise repeatable.
-std::vector<torch::Tensor> gram_sampled(torch::Tensor X, torch::Tensor cols) {
+std::vector<torch::Tensor> gram_sampled(torch::Tensor X, torch::Tensor cols,
+                                        bool center) {
+  TORCH_CHECK(!center, "gram(center=True) does not take cols=: the sampled ",
+              "Grams are centred already");
   check_matrix(X);
   check_i32(cols, 2, "cols");
   TORCH_CHECK(cols.device() == X.device(), "cols: expected X's device");
@@ -528,7 +541,9 @@ torch::Tensor colsel_rowlist(std::vector<torch::Tensor> rows, int64_t mode,
   return out;
 }
 
-torch::Tensor gram_rowlist(std::vector<torch::Tensor> rows) {
+torch::Tensor gram_rowlist(std::vector<torch::Tensor> rows, bool center) {
+  TORCH_CHECK(!center, "gram(center=True) does not take a row list: stack ",
+              "the rows into an (n, d) matrix");
   const RowPtrTable tbl = check_row_list(rows, "gram");
   const int n = (int)rows.size();
   const long d = (long)rows[0].numel();
@@ -1110,13 +1125,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("rows"), py::kw_only(), py::arg("coeffs"));
   m.def("group_mean_rows", &group_mean_rows);
   m.def("bucket_mean", &bucket_mean);
-  m.def("gram", &gram);
+  m.def("gram", &gram,
+        "X X^T; center=True: the column-centred Gram, n <= 128 (K22)",
+        py::arg("X"), py::arg("center") = false);
   m.def("gram", &gram_sampled,
         "sampled centred Grams of DnC (K15): (Gc, bad)", py::arg("X"),
-        py::kw_only(), py::arg("cols"));
+        py::kw_only(), py::arg("cols"), py::arg("center") = false);
   m.def("gram", &gram_rowlist,
         "Gram of a list of n <= 64 1-D device rows, read in place (K19)",
-        py::arg("rows"));
+        py::arg("rows"), py::arg("center") = false);
   m.def("krum_select", &krum_select, py::arg("G"), py::arg("f"), py::arg("q"),
         py::arg("iterative") = false);
   m.def("krum_select", &agr_search,

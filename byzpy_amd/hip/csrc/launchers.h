@@ -175,6 +175,34 @@ void launch_rsel(int mode, const T* X, T* out, unsigned int* state, float* med,
 template <typename T>
 void launch_gram(const T* X, float* G, int n, long d, hipStream_t stream);
 
+// gram_centered.hip (K22): Gc = (X - 1 mu^T)(X - 1 mu^T)^T, mu_j the mean of
+// column j's finite entries (0 if none), in one pass over X: a workgroup owns
+// all n rows of its K-slab, so it centres each staged chunk in LDS before the
+// MFMAs. bf16 rounds x - mu once. Non-finite entries stay non-finite: such a
+// row has a non-finite Gc_ii and row / column, every other entry is clean.
+// Partials are ADDED into the caller-zeroed (n, n) Gc; a second launch
+// mirrors the upper triangle, so Gc is symmetric bit for bit.
+// 1 <= n <= GRAM_CENTERED_MAX_N, d >= 1, any alignment.
+constexpr int GRAM_CENTERED_MAX_N = 128;
+constexpr int GRAM_CENTERED_CHUNK_BYTES = 32 * 1024;  // one LDS buffer
+// rg: 16-row groups the kernel is built for (1, 2, 4 or 8). A chunk is
+// CHUNK_BYTES / (16 rg elem_bytes) columns; slabs are a whole number of
+// chunks, as many as it takes to bring the grid to about four workgroups
+// per CU, and one chunk each below that: the grid fills the device from
+// d = 256 chunks up.
+inline void gram_centered_geometry(int n, long d, int elem_bytes, int& rg,
+                                   long& blocks, long& k_per_block) {
+  rg = n <= 16 ? 1 : (n <= 32 ? 2 : (n <= 64 ? 4 : 8));
+  const long bk = GRAM_CENTERED_CHUNK_BYTES / (16 * rg * elem_bytes);
+  const long chunks = (d + bk - 1) / bk;
+  const long per_block = (chunks + 1023) / 1024;
+  blocks = (chunks + per_block - 1) / per_block;
+  k_per_block = per_block * bk;
+}
+template <typename T>
+void launch_gram_centered(const T* X, float* Gc, int n, long d,
+                          hipStream_t stream);
+
 // gram.hip / subsets.hip (K15, DnC). Row cap of both DnC kernels: the Gram
 // kernel's register blocks and the selection kernel's register-resident
 // matrix are sized by it.

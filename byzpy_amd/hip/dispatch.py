@@ -119,8 +119,59 @@ def mean_of_medians(
 # -- pairwise distances / Krum (K4, K5) -------------------------------------
 
 
-def gram(X: torch.Tensor) -> torch.Tensor:
-    """X @ X.T with f32 accumulation; MFMA split-K kernel on device."""
+# Row cap of gram(X, center=True) (GRAM_CENTERED_MAX_N in csrc/launchers.h).
+GRAM_CENTERED_MAX_N = 128
+
+
+def _gram_centered_torch(X: torch.Tensor) -> torch.Tensor:
+    """The centred Gram as torch ops: the kernel's arithmetic in kind (f32,
+    finite-aware column mean, one bf16 rounding of x - mu for bf16 input), at
+    the cost of three more passes over X and two (n, d) f32 temporaries."""
+    Xf = X.float()
+    fin = torch.isfinite(Xf)
+    mu = torch.where(fin, Xf, torch.zeros_like(Xf)).sum(dim=0)
+    mu = mu / fin.sum(dim=0).clamp(min=1)
+    Xc = Xf - mu[None, :]
+    if X.dtype == torch.bfloat16:
+        Xc = Xc.bfloat16().float()
+    return Xc @ Xc.T
+
+
+def gram(X: torch.Tensor, center: bool = False) -> torch.Tensor:
+    """X @ X.T with f32 accumulation; MFMA split-K kernel on device.
+
+    ``center=True`` (K22, csrc/gram_centered.hip): the Gram of the rows
+    centred by their column mean, Gc = (X - 1 mu^T)(X - 1 mu^T)^T. Squared
+    distances G_ii + G_jj - 2 G_ij are the same on either Gram, but on the
+    raw one their f32 cancellation error is relative to ||x||^2, and rows
+    that share a large component (parameter vectors, momenta, late
+    gradients) are then told apart by summation noise; on the centred one it
+    is relative to ||y||^2, y_i = x_i - mu. Accuracy model: f32 input leaves
+    accumulation error only, relative to ||y||^2. bf16 input rounds y once
+    (an element moves by 2^-9 of itself in the mean, 2^-8 at worst), so a
+    distance is off by about 2^-9 (||y_i|| + ||y_j||): under 2^-7 of D_ij for rows scattered round
+    their mean; a pair far closer to each other than to the mean (a mimic
+    pair) is resolved only down to 2^-9 of its distance from the mean.
+    mu_j is the mean over column j's finite entries (0 if none) and a
+    non-finite entry stays non-finite: a row holding inf or NaN has a
+    non-finite Gc_ii and row / column of Gc, every other entry is clean, so
+    "non-finite diagonal = dead row" keeps working downstream.
+
+    Device matrices of n <= GRAM_CENTERED_MAX_N rows (f32 or bf16, any d)
+    take one pass over X in one kernel. More rows, other dtypes and CPU
+    tensors take ``_gram_centered_torch``: three more passes over X and two
+    (n, d) f32 temporaries. Row lists are not taken: stack them first."""
+    if center:
+        if _row_list(X):
+            raise ValueError("gram(center=True) takes an (n, d) matrix, not a row list")
+        if (
+            _gpu(X)
+            and X.dtype in (torch.float32, torch.bfloat16)
+            and 1 <= X.shape[0] <= GRAM_CENTERED_MAX_N
+            and X.shape[1] >= 1
+        ):
+            return _hip.require().gram(X.contiguous(), center=True)
+        return _gram_centered_torch(X)
     if _row_list(X):
         return _hip.require().gram(list(X))
     if _gpu(X):
@@ -279,39 +330,47 @@ def nearest_rows_from_gram(G: torch.Tensor, k: int) -> torch.Tensor:
     return torch.topk(sq_dists_from_gram(G), k=k, dim=-1, largest=False).indices
 
 
-def pairwise_sq_dists(X: torch.Tensor) -> torch.Tensor:
-    if _gpu(X):
-        return sq_dists_from_gram(gram(X))
+# ``centered=True`` on the distance rules below takes the distances from
+# gram(X, center=True) and feeds the same helpers: the rule is unchanged, the
+# distances of near-equal rows are resolved (see gram). CPU tensors then take
+# the same chain on gram's torch fallback, not the functional oracle.
+
+
+def pairwise_sq_dists(X: torch.Tensor, centered: bool = False) -> torch.Tensor:
+    if _gpu(X) or centered:
+        return sq_dists_from_gram(gram(X, center=centered))
     return F.pairwise_sq_dists(X)
 
 
-def multi_krum_scores(X: torch.Tensor, f: int) -> torch.Tensor:
+def multi_krum_scores(X: torch.Tensor, f: int, centered: bool = False) -> torch.Tensor:
     n = X.shape[0]
     if n - f - 1 < 1:
         raise ValueError(f"need n - f - 1 >= 1, got n={n}, f={f}")
-    if _gpu(X):
-        return krum_scores_from_gram(gram(X), f)
+    if _gpu(X) or centered:
+        return krum_scores_from_gram(gram(X, center=centered), f)
     return F.multi_krum_scores(X, f)
 
 
-def multi_krum(X: torch.Tensor, f: int, q: int) -> torch.Tensor:
-    if _row_list(X) or _gpu(X):
-        return mean_rows(X, krum_winners_from_gram(gram(X), f, q))
+def multi_krum(X: torch.Tensor, f: int, q: int, centered: bool = False) -> torch.Tensor:
+    if _row_list(X) or _gpu(X) or centered:
+        G = gram(X, center=centered)
+        return mean_rows(X, krum_winners_from_gram(G, f, q))
     return F.multi_krum(X, f, q)
 
 
-def krum(X: torch.Tensor, f: int) -> torch.Tensor:
+def krum(X: torch.Tensor, f: int, centered: bool = False) -> torch.Tensor:
     if _row_list(X):
         # the q = 1 mean is the winner itself, and it never visits the host
-        return mean_rows(X, krum_winners_from_gram(gram(X), f, 1))
+        G = gram(X, center=centered)
+        return mean_rows(X, krum_winners_from_gram(G, f, 1))
     if _gpu(X) and X.shape[0] <= 512:
-        idx = krum_winners_from_gram(gram(X), f, 1)
+        idx = krum_winners_from_gram(gram(X, center=centered), f, 1)
         return X[idx.long()[0]].clone()
-    scores = multi_krum_scores(X, f)
+    scores = multi_krum_scores(X, f, centered)
     return X[int(torch.argmin(scores))].clone()
 
 
-def bulyan(X: torch.Tensor, f: int) -> torch.Tensor:
+def bulyan(X: torch.Tensor, f: int, centered: bool = False) -> torch.Tensor:
     """Bulyan (El Mhamdi et al. 2018): Gram -> n - 2f rows by iterated Krum
     -> per coordinate the mean of the n - 4f selected values closest to
     their median. On device: MFMA Gram, one selection launch, one indexed
@@ -321,7 +380,7 @@ def bulyan(X: torch.Tensor, f: int) -> torch.Tensor:
     _check_bulyan(n, f)
     if f == 0:
         return mean_of_medians(X, 0)
-    sel = bulyan_select_from_gram(gram(X), f)
+    sel = bulyan_select_from_gram(gram(X, center=centered), f)
     return mean_of_medians(X, 2 * f, rows=sel)
 
 
@@ -761,7 +820,22 @@ def combine_rows(X, a: torch.Tensor) -> torch.Tensor:
     return (a[keep].double() @ X[keep].double()).to(X.dtype)
 
 
-def solver_gram(X) -> torch.Tensor:
+def solver_gram(X, centered: bool = False) -> torch.Tensor:
+    """The Gram the K20 / K21 solvers run on. ``centered=True``: the centred
+    one (gram(X, center=True)), which is exact for a loop whose coefficients
+    sum to 1 throughout, since then sum_i a_i (x_i - mu) = z - mu and every
+    distance and shift is that of the raw rows. Only Weiszfeld from the mean
+    is such a loop here; the callers refuse the rest."""
+    if centered:
+        if _row_list(X):
+            X = torch.stack(list(X))
+        if _gramfp_fused(X):
+            return gram(X, center=True)
+        Xd = X.double()
+        fin = torch.isfinite(Xd)
+        mu = torch.where(fin, Xd, torch.zeros_like(Xd)).sum(dim=0)
+        Xd = Xd - (mu / fin.sum(dim=0).clamp(min=1))[None, :]
+        return Xd @ Xd.T
     if _gramfp_fused(X):
         return gram(X)
     Xd = X.double()
@@ -792,16 +866,25 @@ def mixed_gram(G: torch.Tensor, mix: torch.Tensor):
 
 
 def _geometric_median_gram(
-    X, *, tol, max_iter, eps, init, fixed_iters, init_z, mix=None, G=None
+    X, *, tol, max_iter, eps, init, fixed_iters, init_z, mix=None, G=None,
+    centered=False,
 ) -> torch.Tensor:
     """geometric_median(solver="gram"). ``init="mean"``: a0 is uniform over
     the live rows. ``init="median"`` / ``init_z``: z0 is outside the span but
     the first update is not, so that step uses real distances
     (row_center_sqdists, one more pass) and the solver runs the rest; its
     shift is not tested. ``mix`` (m, n) runs the rule on the mixed rows
-    (mixed_gram) without forming them; ``G`` passes a Gram already at hand."""
+    (mixed_gram) without forming them; ``G`` passes a Gram already at hand.
+    ``centered`` solves on the centred Gram (solver_gram): mean init only,
+    where the distances resolve rows down to 2^-11 of ||x_i - mu||, not of
+    ||x_i||; the combine still reads the raw rows, right because sum a = 1."""
     if init not in ("median", "mean"):
         raise ValueError("init must be 'median' or 'mean'")
+    if centered and (init != "mean" or init_z is not None):
+        raise ValueError(
+            "centered=True needs init='mean' and no init_z: the coefficients "
+            "must sum to 1 from the first step"
+        )
     if _row_list(X) and not _gramfp_fused(X):
         X = torch.stack(list(X))
     fused = _gramfp_fused(X)
@@ -816,7 +899,7 @@ def _geometric_median_gram(
         else:
             z0 = median(X)
     if G is None:
-        G = solver_gram(X)
+        G = solver_gram(X, centered)
     W = None
     if mix is not None:
         G, W = mixed_gram(G, mix)
@@ -887,6 +970,7 @@ def geometric_median(
     fixed_iters: Optional[int] = None,
     init_z: Optional[torch.Tensor] = None,
     solver: str = "iterative",
+    centered: bool = False,
 ) -> torch.Tensor:
     """Weiszfeld fixed point. ``fixed_iters`` runs exactly that many
     iterations with NO convergence polls — fully async (no host sync), so
@@ -895,12 +979,16 @@ def geometric_median(
     starts from a caller-provided center (e.g. the previous gossip
     round's output — the fixed point barely moves between rounds, so a
     handful of iterations replaces a cold median init + long descent).
-    ``solver="gram"`` runs the loop on the Gram instead (K20, above)."""
+    ``solver="gram"`` runs the loop on the Gram instead (K20, above);
+    with ``init="mean"`` it may run on the centred Gram (``centered=True``,
+    K22). Any other use of ``centered`` is a ValueError."""
     _check_solver(solver)
+    if centered and solver != "gram":
+        raise ValueError("centered=True needs solver='gram'")
     if solver == "gram":
         return _geometric_median_gram(
             X, tol=tol, max_iter=max_iter, eps=eps, init=init,
-            fixed_iters=fixed_iters, init_z=init_z,
+            fixed_iters=fixed_iters, init_z=init_z, centered=centered,
         )
     if not _gpu(X) or X.shape[0] > 1024:
         # extension's weiszfeld_iter TORCH_CHECKs n <= 1024; the torch
@@ -1039,8 +1127,12 @@ def centered_clipping(
     eps: float = 1e-12,
     init: str = "mean",
     solver: str = "iterative",
+    centered: bool = False,
 ) -> torch.Tensor:
     _check_solver(solver)
+    if centered:
+        # a clipping step's coefficients do not sum to 1
+        raise ValueError("centered clipping does not run on the centred Gram")
     if solver == "gram":
         return _centered_clipping_gram(X, c_tau=c_tau, M=M, eps=eps, init=init)
     if not _gpu(X) or X.shape[0] > 1024:
@@ -1075,9 +1167,9 @@ def bucketing(
     return F.bucketing(X, bucket_size, perm)
 
 
-def nnm(X: torch.Tensor, f: int) -> torch.Tensor:
-    if _gpu(X):
-        idx = nearest_rows_from_gram(gram(X), X.shape[0] - f)
+def nnm(X: torch.Tensor, f: int, centered: bool = False) -> torch.Tensor:
+    if _gpu(X) or centered:
+        idx = nearest_rows_from_gram(gram(X, center=centered), X.shape[0] - f)
         return group_mean_rows(X, idx)
     return F.nnm(X, f)
 
@@ -1876,7 +1968,8 @@ def _caf_on_gram(X, f: int, power_iters: int) -> torch.Tensor:
 
 
 def caf(
-    X: torch.Tensor, f: int, *, power_iters: int = 3, solver: str = "iterative"
+    X: torch.Tensor, f: int, *, power_iters: int = 3, solver: str = "iterative",
+    centered: bool = False,
 ) -> torch.Tensor:
     """Covariance-agnostic filter on fused K9 kernels (reference
     caf.py:133-184): caf_matvec computes s = (X - mu) @ v, caf_colsum
@@ -1890,6 +1983,9 @@ def caf(
     import os
 
     _check_solver(solver)
+    if centered:
+        # the filter re-centres by its own weighted mean every round
+        raise ValueError("CAF does not run on the centred Gram")
     if solver == "gram":
         return _caf_on_gram(X, int(f), int(power_iters))
     n = X.shape[0]

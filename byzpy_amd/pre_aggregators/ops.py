@@ -126,26 +126,34 @@ class Bucketing(PreAggregator):
 
 class NearestNeighborMixing(PreAggregator):
     """Replace x_i with the mean of its n-f nearest neighbours (incl. self);
-    feature-chunked partial Gram on CPU pools (nnm.py:182-187)."""
+    feature-chunked partial Gram on CPU pools (nnm.py:182-187).
+
+    ``centered=True``: the neighbour sets come from the column-centred Gram
+    (``D.gram(X, center=True)``, K22), which resolves rows that share a
+    large component. The CPU pool's chunked path ignores the flag (it sums
+    raw feature-chunk Grams)."""
 
     name = "pre-agg/nnm"
     supports_subtasks = True
     max_subtasks_inflight = 0
 
-    def __init__(self, f: int, *, feature_chunk_size: int = 8192) -> None:
+    def __init__(
+        self, f: int, *, feature_chunk_size: int = 8192, centered: bool = False
+    ) -> None:
         if f < 0:
             raise ValueError("f must be >= 0")
         self.f = int(f)
         self.feature_chunk_size = int(feature_chunk_size)
+        self.centered = bool(centered)
 
     def _pre_aggregate(self, X: torch.Tensor) -> torch.Tensor:
-        return D.nnm(X, self.f)
+        return D.nnm(X, self.f, centered=self.centered)
 
     def membership(self, X: torch.Tensor) -> torch.Tensor:
         """The (n, n) 0/1 matrix of the mixing, on X's device: row i marks
         the n - f nearest rows of row i (itself included), the indices
         ``_pre_aggregate`` averages."""
-        return self.membership_from_gram(D.gram(X))
+        return self.membership_from_gram(D.gram(X, center=self.centered))
 
     def membership_from_gram(self, G: torch.Tensor) -> torch.Tensor:
         """``membership(X)`` from X's Gram, for a caller that needs the Gram
