@@ -888,7 +888,9 @@ torch::Tensor smea_select(torch::Tensor G, torch::Tensor combos) {
   const int n = (int)G.size(0);
   const int C = (int)combos.size(0);
   const int m = (int)combos.size(1);
-  TORCH_CHECK(m >= 1 && m <= 64 && C >= 1);
+  TORCH_CHECK(m >= 1 && m <= 64 && C >= 1, "smea_select(G, combos) supports ",
+              "1 <= m <= 64 rows per combo and C >= 1 combos, got m = ", m,
+              ", C = ", C);
   auto best = torch::full({1}, -1, G.options().dtype(torch::kInt64));
   launch_smea_select(f32(G), i32(combos), n, m, C,
                      ptr<unsigned long long>(best), cur_stream());
@@ -999,12 +1001,15 @@ std::vector<torch::Tensor> mda_select(torch::Tensor D2, int64_t f,
   // all-ones pattern decodes to NaN and every comparison goes false.
   // An optional achievable upper bound seeds the key so pass 1 prunes
   // from the start (one ulp up so strict < can re-find an exact tie).
+  // A bound of +inf (every subset holds an infinite distance) or NaN is no
+  // bound: the key stays at +inf, where pass 2 still accepts dj == +inf.
   torch::Tensor best;
   if (ub.has_value()) {
     check_f32_scalar(*ub, "ub");
-    auto bits = torch::nan_to_num(ub.value(), 0.0, 3.0e38, 0.0)
-                    .view(torch::kInt32);
-    best = (bits + 1).bitwise_or((int)0x80000000).contiguous();
+    const double inf = INFINITY;
+    auto bits = torch::nan_to_num(ub.value(), inf, inf, 0.0).view(torch::kInt32);
+    best = (bits + 1).clamp_max((int)0x7F800000)
+               .bitwise_or((int)0x80000000).contiguous();
   } else {
     best = torch::full({1}, (int)0xFF800000, i32_like(D2));
   }

@@ -37,7 +37,10 @@ torch::Tensor mda_search(torch::Tensor D2in, int64_t f) {
       int pick = -1;
       double pick_cost = std::numeric_limits<double>::infinity();
       for (int j = 0; j < n; ++j)
-        if (!used[j] && maxd[j] < pick_cost) { pick_cost = maxd[j]; pick = j; }
+        if (!used[j] && (pick < 0 || maxd[j] < pick_cost)) {
+          pick_cost = maxd[j];  // pick < 0: rows at +inf are candidates too
+          pick = j;
+        }
       used[pick] = 1;
       cur.push_back(pick);
       diam = std::max(diam, pick_cost);
@@ -56,26 +59,33 @@ torch::Tensor mda_search(torch::Tensor D2in, int64_t f) {
   std::sort(order.begin(), order.end(),
             [&](int a, int b) { return rowsum[a] < rowsum[b]; });
 
+  // A node lists its viable candidates first: those compatible with every
+  // chosen row at the current bound. A completion needs `need` of them, so
+  // fewer ends the node. Counting positions alone (oi <= n - need) lets the
+  // search wander through subsets of a tight cluster that has too few rows
+  // left, which is exponential when the rows it cannot use sort last.
   std::vector<int> chosen;
   chosen.reserve(m);
+  std::vector<std::vector<std::pair<int, double>>> viable(m + 1);
   std::function<void(int, double)> dfs = [&](int start, double diam) {
     if ((int)chosen.size() == m) {
       if (diam < best_diam) { best_diam = diam; best = chosen; }
       return;
     }
     const int need = m - (int)chosen.size();
-    for (int oi = start; oi <= n - need; ++oi) {
+    auto& cands = viable[chosen.size()];
+    cands.clear();
+    for (int oi = start; oi < n; ++oi) {
       const int j = order[oi];
       double dj = diam;
-      bool ok = true;
-      for (int c : chosen) {
-        const double dc = D[c][j];
-        if (dc >= best_diam) { ok = false; break; }
-        if (dc > dj) dj = dc;
-      }
-      if (!ok || dj >= best_diam) continue;
-      chosen.push_back(j);
-      dfs(oi + 1, dj);
+      for (int c : chosen) dj = std::max(dj, D[c][j]);
+      if (dj < best_diam) cands.emplace_back(oi, dj);
+    }
+    for (int k = 0; k + need <= (int)cands.size(); ++k) {
+      const double dj = cands[k].second;
+      if (dj >= best_diam) continue;  // the bound fell since the listing
+      chosen.push_back(order[cands[k].first]);
+      dfs(cands[k].first + 1, dj);
       chosen.pop_back();
     }
   };
@@ -90,17 +100,22 @@ torch::Tensor mda_search(torch::Tensor D2in, int64_t f) {
   std::vector<int> lex;
   lex.reserve(m);
   bool found = false;
+  std::vector<std::vector<int>> viable2(m + 1);
   std::function<void(int)> dfs2 = [&](int start) {
     if (found) return;
     if ((int)lex.size() == m) { best = lex; found = true; return; }
     const int need = m - (int)lex.size();
-    for (int j = start; j <= n - need && !found; ++j) {
+    auto& cands = viable2[lex.size()];
+    cands.clear();
+    for (int j = start; j < n; ++j) {
       bool ok = true;
       for (int c : lex)
-        if (D[c][j] > bound) { ok = false; break; }
-      if (!ok) continue;
-      lex.push_back(j);
-      dfs2(j + 1);
+        if (!(D[c][j] <= bound)) { ok = false; break; }
+      if (ok) cands.push_back(j);
+    }
+    for (int k = 0; k + need <= (int)cands.size() && !found; ++k) {
+      lex.push_back(cands[k]);
+      dfs2(cands[k] + 1);
       lex.pop_back();
     }
   };

@@ -36,6 +36,8 @@ DEV u32 f32_key(float v) {
 // ---------------------------------------------------------------------------
 
 constexpr int SMEA_SWEEPS = 10;
+// a rotation is skipped when |a_pq| <= this * sqrt(a_pp a_qq): f32 unit roundoff
+constexpr float SMEA_SKIP_EPS = 0x1p-24f;
 
 // one 64-lane wave per subset; LDS: A[m*m] + rows[m]
 __global__ void __launch_bounds__(64)
@@ -78,9 +80,14 @@ smea_select_kernel(const float* __restrict__ G, const int* __restrict__ combos,
       for (int p = 0; p < m - 1; ++p) {
         for (int q = p + 1; q < m; ++q) {
           const float apq = A[p * m + q];
-          if (fabsf(apq) < 1e-12f) continue;
           const float app = A[p * m + p];
           const float aqq = A[q * m + q];
+          // skip relative to the pair's own scale: G and 2^k G take the same
+          // decisions (an absolute cut skipped every rotation of a small G
+          // and left lam = the largest diagonal entry). Two roots, so that
+          // the product neither underflows nor overflows.
+          if (fabsf(apq) <= SMEA_SKIP_EPS * (sqrtf(fabsf(app)) * sqrtf(fabsf(aqq))))
+            continue;
           const float tau = (aqq - app) / (2.0f * apq);
           const float t = (tau >= 0.0f ? 1.0f : -1.0f) /
                           (fabsf(tau) + sqrtf(1.0f + tau * tau));
@@ -215,18 +222,22 @@ mda_dfs_kernel(const float* __restrict__ D2g, const int* __restrict__ prefixes,
       // node count 12x — collaborative pruning needs tight bounds)
       const float cur_best = FIND ? bound : read_best();
       const int start = cand[depth];
-      const int maxj = n - (need - depth - 1);
       // WAVE-PARALLEL candidate scan: n <= 64, so one ballot evaluates
       // every remaining candidate at this level at once
       const int j = start + lane;
       bool ok = false;
       float dj = 0.0f;
-      if (j < maxj) {
+      if (j < n) {
         dj = fmaxf(pdiam[depth], maxd[depth * n + j]);
         ok = FIND ? (dj <= cur_best) : (dj < cur_best);
       }
       const unsigned long long mask = __ballot(ok);
-      if (mask == 0ull) {
+      // A completion takes need - depth of the rows that are viable here, so
+      // fewer ends the level. (Counting positions alone, j < n - (need -
+      // depth - 1), walks every subset of a tight cluster that is one row
+      // short: exponential when the rows it cannot use have high indices.)
+      // The first viable row then has need - depth - 1 rows after it.
+      if (__popcll(mask) < need - depth) {
         --depth;  // level exhausted: backtrack
         continue;
       }

@@ -1717,28 +1717,35 @@ def agr_coord(
 # -- remaining ops: torch composition on either device ----------------------
 
 
-def minimum_diameter_averaging(X: torch.Tensor, f: int) -> torch.Tensor:
-    n = X.shape[0]
+def mda_subset_device(D2: torch.Tensor, f: int) -> Optional[torch.Tensor]:
+    """The lexicographically smallest minimum-diameter (n - f)-subset of the
+    device f32 (n, n) D2 as an int32 index tensor, found by the two-pass
+    branch-and-bound of subsets.hip: no host D2 copy, one host sync. None
+    where the search does not apply (n > 64, or n - f outside 2 .. n - 1) or
+    found nothing (a NaN in D2): the caller falls back to the host search."""
+    n = D2.shape[0]
     m = n - f
+    if not (n <= 64 and 2 <= m < n):
+        return None
+    # Seed the shared bound with a cheap anchor-greedy upper bound (diameter
+    # of each row's m nearest rows) so pass 1 prunes like the host B&B
+    # instead of starting from +inf.
+    idxn = torch.topk(D2, k=m, dim=1, largest=False).indices
+    sub = D2[idxn[:, :, None], idxn[:, None, :]]  # (n, m, m)
+    ub = sub.amax(dim=(1, 2)).min()
+    found, subsets = _hip.require().mda_select(D2, int(f), ub)
+    if not bool(found.any()):
+        return None
+    # the first found prefix holds the winner: a cumsum one-hot mask
+    first = ((found.cumsum(0) == 1) & (found == 1)).to(subsets.dtype)
+    return (subsets * first[:, None]).sum(dim=0).to(torch.int32)
+
+
+def minimum_diameter_averaging(X: torch.Tensor, f: int) -> torch.Tensor:
     if _gpu(X):
         D2 = pairwise_sq_dists(X)
-        if n <= 64 and 2 <= m < n:
-            # fully device-side two-pass branch-and-bound (subsets.hip):
-            # no host D2 copy, no host sync — the winning (lex-smallest
-            # optimal) subset is selected with a cumsum one-hot mask.
-            # Seed the shared bound with a cheap anchor-greedy upper
-            # bound (diameter of each row's m nearest rows) so pass 1
-            # prunes like the host B&B instead of starting from +inf.
-            idxn = torch.topk(D2, k=m, dim=1, largest=False).indices
-            sub = D2[idxn[:, :, None], idxn[:, None, :]]  # (n, m, m)
-            ub = sub.amax(dim=(1, 2)).min()
-            found, subsets = _hip.require().mda_select(D2, int(f), ub)
-            if not bool(found.any()):  # degenerate (e.g. all-inf D2)
-                subset = F.mda_subset(D2, f)
-                idx = torch.tensor(subset, device=X.device, dtype=torch.long)
-                return mean_rows(X, idx)
-            first = ((found.cumsum(0) == 1) & (found == 1)).to(subsets.dtype)
-            subset_t = (subsets * first[:, None]).sum(dim=0).to(torch.int32)
+        subset_t = mda_subset_device(D2, f)
+        if subset_t is not None:
             return mean_rows(X, subset_t)
         subset = F.mda_subset(D2, f)
         idx = torch.tensor(subset, device=X.device, dtype=torch.long)

@@ -457,24 +457,26 @@ def mda_subset(D2: torch.Tensor, f: int) -> Tuple[int, ...]:
             best_diam = diam
             best = tuple(sorted(chosen))
             return
-        # not enough remaining to complete the subset
-        remaining = n - start
-        if remaining < m - len(chosen):
-            return
+        # list the rows still viable at the current bound: a completion
+        # needs `need` of them (counting positions alone walks every subset
+        # of a tight cluster that is a row short; mda_host.cpp has the same cut)
+        need = m - len(chosen)
+        cands = []
         for j in range(start, n):
             dj = diam
-            ok = True
             for c in chosen:
                 dc = D[c][order[j]]
-                if dc >= best_diam:
-                    ok = False
-                    break
                 if dc > dj:
                     dj = dc
-            if ok:
-                chosen.append(order[j])
-                dfs(j + 1, chosen, dj)
-                chosen.pop()
+            if dj < best_diam:
+                cands.append((j, dj))
+        for k in range(len(cands) - need + 1):
+            j, dj = cands[k]
+            if dj >= best_diam:  # the bound fell since the listing
+                continue
+            chosen.append(order[j])
+            dfs(j + 1, chosen, dj)
+            chosen.pop()
 
     dfs(0, [], 0.0)
 
@@ -487,12 +489,12 @@ def mda_subset(D2: torch.Tensor, f: int) -> Tuple[int, ...]:
         if len(lex) == m:
             return True
         need = m - len(lex)
-        for j in range(start, n - need + 1):
-            if all(D[c][j] <= bound for c in lex):
-                lex.append(j)
-                if dfs2(j + 1):
-                    return True
-                lex.pop()
+        cands = [j for j in range(start, n) if all(D[c][j] <= bound for c in lex)]
+        for j in cands[: max(0, len(cands) - need + 1)]:  # `need` viable rows must remain
+            lex.append(j)
+            if dfs2(j + 1):
+                return True
+            lex.pop()
         return False
 
     if dfs2(0):
