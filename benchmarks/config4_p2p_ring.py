@@ -45,6 +45,10 @@ def main() -> None:
     p.add_argument("--grouped", action="store_true",
                    help="batch ALL node updates into grouped kernels "
                         "(one launch pair per Weiszfeld iteration)")
+    p.add_argument("--shared-gram", action="store_true",
+                   help="the whole round on ONE Gram of theta (K23): Gram, "
+                        "one solver launch for all nodes, one batched "
+                        "combine; GeometricMedian(solver='gram', init='mean')")
     p.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
     args = p.parse_args()
     dev = torch.device(args.device)
@@ -104,7 +108,19 @@ def main() -> None:
             warm_grouped["Z"] = Z
         theta.copy_(Z.to(theta.dtype))
 
+    gossip_groups = D.gossip_groups(
+        [[i] + topo.in_neighbors(i) for i in range(args.nodes)], dev
+    )
+
+    def round_once_shared_gram():
+        theta.copy_(D.gossip_geometric_median(
+            theta, gossip_groups, nnm_f=args.f, fixed_iters=fixed or 4,
+        ))
+
     def round_once():
+        if args.shared_gram:
+            round_once_shared_gram()
+            return
         if args.grouped:
             round_once_grouped()
             return

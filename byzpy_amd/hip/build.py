@@ -20,7 +20,8 @@ OUT_SO = PKG_DIR / "_hip_ops.so"
 BUILD_DIR = PKG_DIR.parent / "build" / "hip"
 
 SOURCES = ["colsel.hip", "colsel_mix.hip", "rsel.hip", "rowops.hip", "gram.hip",
-           "gram_centered.hip", "rowptrs.hip", "krumsel.hip", "subsets.hip", "gramfp.hip", "attacks.hip",
+           "gram_centered.hip", "rowptrs.hip", "krumsel.hip", "subsets.hip", "gramfp.hip", "combine_batched.hip",
+           "attacks.hip",
            "mda_host.cpp", "bind.cpp"]
 HEADERS = ["common.h", "launchers.h", "mda_host.h", "oem_sort.h", "selnet.h",
            "colsel_shared.h"]
@@ -37,6 +38,7 @@ EXTRA_FLAGS = {
     "rowptrs.hip": _NO_PK_F32,
     "gramfp.hip": _NO_PK_F32,
     "gram_centered.hip": _NO_PK_F32,
+    "combine_batched.hip": _NO_PK_F32,
 }
 
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")

@@ -582,6 +582,27 @@ void check_coeffs(const torch::Tensor& coeffs, int64_t n,
   TORCH_CHECK(coeffs.device() == device, "coeffs: expected the rows' device");
 }
 
+// mean_rows(X, coeffs=A) with a 2-D A (M, n): out (M, d) = A X in X's dtype
+// (combine_batched.hip, K23). X is checked by the caller.
+torch::Tensor combine_rows_batched(const torch::Tensor& X,
+                                   const torch::Tensor& coeffs) {
+  const int64_t n = X.size(0), M = coeffs.size(0);
+  const long d = (long)X.size(1);
+  TORCH_CHECK(coeffs.is_cuda() && coeffs.scalar_type() == torch::kFloat32 &&
+                  coeffs.is_contiguous() && coeffs.size(1) == n,
+              "coeffs: expected an f32 contiguous device matrix (M, ", n, ")");
+  TORCH_CHECK(coeffs.device() == X.device(), "coeffs: expected the rows' device");
+  TORCH_CHECK(M >= 1 && M <= GRAMFP_MAX_N, "mean_rows(coeffs=) supports ",
+              "1 <= M <= ", GRAMFP_MAX_N, " rows of coefficients, got ", M);
+  auto out = torch::empty({M, d}, X.options());
+  by_dtype(X, [&](auto tag) {
+    using T = TAG_T(tag);
+    launch_combine_batched<T>(ptr<T>(X), f32(coeffs), ptr<T>(out), (int)n,
+                              (int)M, d, cur_stream());
+  });
+  return out;
+}
+
 // mean_rows(X, coeffs=a): out = sum_i a[i] X[i] in X's dtype (rowptrs.hip).
 // Not normalised; rows with a[i] == 0 are not read. n <= GRAMFP_MAX_N.
 torch::Tensor combine_rows(torch::Tensor X, torch::Tensor coeffs) {
@@ -591,6 +612,7 @@ torch::Tensor combine_rows(torch::Tensor X, torch::Tensor coeffs) {
   TORCH_CHECK(n >= 1 && n <= GRAMFP_MAX_N, "mean_rows(coeffs=) supports ",
               "1 <= n <= ", GRAMFP_MAX_N, ", got ", n);
   TORCH_CHECK(d >= 1, "mean_rows(coeffs=): expected at least one column");
+  if (coeffs.dim() == 2) return combine_rows_batched(X, coeffs);
   check_coeffs(coeffs, n, X.device());
   auto out = torch::empty({d}, X.options());
   by_dtype(X, [&](auto tag) {
@@ -658,6 +680,40 @@ std::vector<torch::Tensor> weiszfeld_gram(torch::Tensor G, torch::Tensor a0,
                                           int64_t iters) {
   return gram_fixed_point(G, a0, GRAMFP_WEISZFELD, eps, tol, 0.0, iters,
                           "weiszfeld_iter");
+}
+
+// weiszfeld_iter(G, groups=, nnm_f=, eps=, tol=, iters=): a whole gossip round
+// solved on the shared Gram (gramfp.hip, K23), one wave per node, one launch.
+// groups int32 (M, m), -1 pads; nnm_f = -1: no mixing. Returns (A f32 (M, n),
+// steps int32 (M,)). No host sync.
+std::vector<torch::Tensor> weiszfeld_gossip(torch::Tensor G,
+                                            torch::Tensor groups,
+                                            int64_t nnm_f, double eps,
+                                            double tol, int64_t iters) {
+  check_gram(G, "G");
+  const int64_t n = G.size(0);
+  TORCH_CHECK(n >= 1 && n <= GRAMFP_MAX_N, "weiszfeld_iter(G, groups=) ",
+              "supports 1 <= n <= ", GRAMFP_MAX_N, ", got ", n);
+  check_i32(groups, 2, "groups");
+  TORCH_CHECK(groups.device() == G.device(), "groups: expected G's device");
+  const int64_t M = groups.size(0), m = groups.size(1);
+  TORCH_CHECK(M >= 1 && M <= GRAMFP_MAX_N && m >= 1 && m <= GOSSIP_MAX_M,
+              "groups: expected (M, m) with 1 <= M <= ", GRAMFP_MAX_N,
+              " and 1 <= m <= ", GOSSIP_MAX_M, ", got (", M, ", ", m, ")");
+  TORCH_CHECK(nnm_f >= -1 && nnm_f < m, "nnm_f: expected -1 (no mixing) or ",
+              "0 <= nnm_f < m, got ", nnm_f);
+  TORCH_CHECK(eps > 0.0 && eps < INFINITY, "eps: expected a finite value > 0, ",
+              "got ", eps);
+  TORCH_CHECK(tol >= 0.0 && tol < INFINITY, "tol: expected a finite value ",
+              ">= 0, got ", tol);
+  TORCH_CHECK(iters >= 0 && iters <= INT_MAX, "iters: expected 0 <= iters <= ",
+              INT_MAX, ", got ", iters);
+  auto A = torch::empty({M, n}, f32_like(G));
+  auto steps = torch::empty({M}, i32_like(G));
+  launch_gossip_solve(f32(G), i32(groups), (int)n, (int)M, (int)m, (int)nnm_f,
+                      eps, tol * tol, (int)iters, f32(A), i32(steps),
+                      cur_stream());
+  return {A, steps};
 }
 
 // cc_iter(G, a0, c_tau=, eps=, iters=): exactly `iters` centered-clipping
@@ -1123,7 +1179,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "mean of rows[idx[i]] over a list of n <= 64 1-D device rows (K19)",
         py::arg("rows"), py::arg("idx"));
   m.def("mean_rows", &combine_rows,
-        "sum_i coeffs[i] X[i], rows under a zero coefficient not read (K20)",
+        "sum_i coeffs[i] X[i], rows under a zero coefficient not read (K20); "
+        "2-D coeffs (M, n): coeffs @ X on the matrix pipe (K23)",
         py::arg("X"), py::kw_only(), py::arg("coeffs"));
   m.def("mean_rows", &combine_rows_rowlist,
         "the same over a list of n <= 64 1-D device rows (K20)",
@@ -1157,6 +1214,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "the Weiszfeld loop on the Gram (K20): (a, steps, shift2)",
         py::arg("G"), py::arg("a0"), py::kw_only(), py::arg("eps"),
         py::arg("tol"), py::arg("iters"));
+  m.def("weiszfeld_iter", &weiszfeld_gossip,
+        "a gossip round solved on the shared Gram (K23): (A, steps)",
+        py::arg("G"), py::kw_only(), py::arg("groups"), py::arg("nnm_f"),
+        py::arg("eps"), py::arg("tol"), py::arg("iters"));
   m.def("weiszfeld_iter_grouped", &weiszfeld_iter_grouped,
         "one Weiszfeld iteration for G independent (m, d) groups");
   m.def("weiszfeld_apply", &weiszfeld_apply);

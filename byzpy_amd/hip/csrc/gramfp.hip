@@ -336,7 +336,183 @@ caf_gram_kernel(const float* __restrict__ G, const float* __restrict__ seeds,
   }
 }
 
+// -- a whole gossip round on one shared Gram (K23) ----------------------------
+//
+// All node states are rows of one matrix, so its Gram G holds every node's
+// neighbourhood sub-Gram G[S, S]. One WAVE solves one node, four nodes to a
+// workgroup: a neighbourhood has m <= 32 rows, so lane r owns row r, a node
+// never leaves its wave, and the loop has no block barrier at all (the K20
+// kernel above pays four a step because it serves n = 128).
+//  - gather: lane r reads row r of the sub-Gram straight into 32 f64
+//    registers (the entries are f32: widening is exact). A padded slot (-1)
+//    is dead, and so is a slot whose G_ii is not finite; entries of dead
+//    pairs and entries that are not finite read as 0.
+//  - NNM (nnm_f >= 0): lane r ranks D_rs = G_rr + G_ss - 2 G_rs over the live
+//    s and keeps the k = max(live - f, 1) nearest, itself included, the lower
+//    slot on a tie: a 32-bit mask per row. G_Y = W G W^T in two halves:
+//    lane r sums its row over each mask j (T = G W^T, to the wave's LDS
+//    tile), lane i sums the rows of T in its own mask; both in slot order,
+//    then one scale by 1 / k^2. A dead row mixes nothing and stays dead.
+//  - loop: K20's, with lane i holding row i of G_Y. The matvec reads the
+//    operand lane by lane (32 fma in slot order), the sums are a 6-level
+//    xor butterfly whose partners add the same two numbers, so every lane
+//    holds the same bits and the wave stops as one.
+//  - pull back c = W^T a, scatter through a wave-private LDS row so that
+//    row i of A is written once, zeros included.
+// f64 throughout, no atomics: the same G bits give the same A bits.
+constexpr int GSP_WAVES = 4;
+constexpr int GSP_M = GOSSIP_MAX_M;
+
+DEV double gsp_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// Orders this wave's LDS accesses, for the compiler: the LDS serves one
+// wave's operations in order.
+DEV void gsp_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// y_lane = sum_j gy[j] x_j, x_j lane j's x
+DEV double gsp_matvec(const double (&gy)[GSP_M], double x) {
+  double y = 0.0;
+#pragma unroll
+  for (int j = 0; j < GSP_M; ++j) y = fma(gy[j], __shfl(x, j, 64), y);
+  return y;
+}
+
+__global__ void __launch_bounds__(GSP_WAVES * 64)
+gossip_solve_kernel(const float* __restrict__ G, const int* __restrict__ groups,
+                    int n, int M, int m, int nnm_f, double eps, double tol2,
+                    int iters, float* __restrict__ A,
+                    int* __restrict__ steps_out) {
+  __shared__ double tile[GSP_WAVES][GSP_M][GSP_M + 1];
+  __shared__ float crow[GSP_WAVES][GRAMFP_MAX_N];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int node = blockIdx.x * GSP_WAVES + wave;
+  if (node >= M) return;  // the whole wave; nothing below is block-wide
+
+  int idx = lane < m ? groups[(long)node * m + lane] : -1;
+  if (idx >= n) idx = -1;
+  double gii = 0.0;
+  int live = 0;
+  if (idx >= 0) {
+    const float gf = G[(long)idx * n + idx];
+    live = fabsf(gf) < INFINITY;
+    if (live) gii = (double)gf;
+  }
+  double gy[GSP_M];
+#pragma unroll
+  for (int s = 0; s < GSP_M; ++s) {
+    const int is = __shfl(idx, s, 64);
+    const int ls = __shfl(live, s, 64);
+    float x = (live && ls) ? G[(long)idx * n + is] : 0.0f;
+    if (!(fabsf(x) < INFINITY)) x = 0.0f;
+    gy[s] = (double)x;
+  }
+  const int nlive = __popcll(__ballot(live));
+
+  unsigned mask = 0;  // row `lane` of the mixing as bits; W = mask / k
+  double inv_k = 1.0;
+  if (nnm_f >= 0) {
+    const int k = nlive - nnm_f > 1 ? nlive - nnm_f : 1;
+    inv_k = 1.0 / (double)k;
+    double dist[GSP_M];
+#pragma unroll
+    for (int s = 0; s < GSP_M; ++s) {
+      const double gss = __shfl(gii, s, 64);
+      const int ls = __shfl(live, s, 64);
+      dist[s] = ls ? gii + gss - 2.0 * gy[s] : (double)INFINITY;
+    }
+#pragma unroll
+    for (int s = 0; s < GSP_M; ++s) {
+      int rank = 0;
+#pragma unroll
+      for (int t = 0; t < GSP_M; ++t)
+        rank += (dist[t] < dist[s]) || (t < s && dist[t] == dist[s]);
+      if (live && dist[s] < (double)INFINITY && rank < k) mask |= 1u << s;
+    }
+    // T = G W^T k: row `lane`, summed over each row j's members
+#pragma unroll
+    for (int j = 0; j < GSP_M; ++j) {
+      const unsigned mj = (unsigned)__shfl((int)mask, j, 64);
+      double t = 0.0;
+#pragma unroll
+      for (int s = 0; s < GSP_M; ++s)
+        if ((mj >> s) & 1u) t += gy[s];
+      if (lane < GSP_M) tile[wave][lane][j] = t;
+    }
+    gsp_fence();
+#pragma unroll
+    for (int j = 0; j < GSP_M; ++j) gy[j] = 0.0;
+    for (int r = 0; r < GSP_M; ++r)
+      if ((mask >> r) & 1u) {
+#pragma unroll
+        for (int j = 0; j < GSP_M; ++j) gy[j] += tile[wave][r][j];
+      }
+#pragma unroll
+    for (int j = 0; j < GSP_M; ++j) {
+      gy[j] *= inv_k * inv_k;
+      if (j == lane) gii = gy[j];
+    }
+  }
+
+  // K20's loop; every quantity is 0 in the lanes that own no live row
+  double a = live ? 1.0 / (double)nlive : 0.0;
+  double u = gsp_matvec(gy, a);
+  double q = gsp_sum(a * u);
+  int steps = 0;
+  for (int it = 0; it < iters; ++it) {
+    const double dist = fmax(sqrt(fmax(gii - 2.0 * u + q, 0.0)), eps);
+    const double c = live ? 1.0 / dist : 0.0;
+    const double sc = gsp_sum(c);
+    const double an = sc > 0.0 ? c / sc : 0.0;
+    const double da = an - a;
+    const double tv = gsp_matvec(gy, da);
+    u += tv;
+    a = an;
+    const double shift2 = gsp_sum(da * tv);
+    q = gsp_sum(a * u);
+    ++steps;
+    // every lane holds the same shift2: the wave stops as one
+    if (tol2 > 0.0 && shift2 <= tol2) break;
+  }
+
+  double c = a;  // coefficients over the rows of X: W^T a
+  if (nnm_f >= 0) {
+    c = 0.0;
+#pragma unroll
+    for (int r = 0; r < GSP_M; ++r) {
+      const unsigned mr = (unsigned)__shfl((int)mask, r, 64);
+      const double ar = __shfl(a, r, 64);
+      if ((mr >> (lane & 31)) & 1u) c += ar;
+    }
+    c *= inv_k;
+  }
+  crow[wave][lane] = 0.0f;
+  crow[wave][lane + 64] = 0.0f;
+  gsp_fence();
+  if (idx >= 0) crow[wave][idx] = (float)c;
+  gsp_fence();
+  for (int j = lane; j < n; j += 64) A[(long)node * n + j] = crow[wave][j];
+  if (lane == 0) steps_out[node] = steps;
+}
+
 }  // namespace
+
+void launch_gossip_solve(const float* G, const int* groups, int n, int M, int m,
+                         int nnm_f, double eps, double tol2, int iters,
+                         float* A, int* steps, hipStream_t stream) {
+  hipLaunchKernelGGL(gossip_solve_kernel,
+                     dim3((M + GSP_WAVES - 1) / GSP_WAVES),
+                     dim3(GSP_WAVES * 64), 0, stream, G, groups, n, M, m, nnm_f,
+                     eps, tol2, iters, A, steps);
+}
 
 void launch_gram_fixed_point(const float* G, const float* a0, int n, int rule,
                              double eps, double tol2, double c_tau, int iters,

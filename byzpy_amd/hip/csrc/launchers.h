@@ -155,6 +155,32 @@ void launch_gram_fixed_point(const float* G, const float* a0, int n, int rule,
 void launch_caf_gram(const float* G, const float* seeds, int n, int f,
                      int power_iters, float* a, float* lam, int* rounds,
                      hipStream_t stream);
+// gramfp.hip (K23): the gossip round's solver. G is the f32 Gram (n, n) of
+// ALL resident rows, groups (M, m) int32 lists per node the rows it
+// aggregates (-1, or an index >= n, pads a ragged neighbourhood; the valid
+// entries of a row are distinct). Per node, one wave: the m x m sub-Gram;
+// with nnm_f >= 0 nearest-neighbour mixing on it (k = max(live - nnm_f, 1)
+// nearest rows by G_rr + G_ss - 2 G_rs, the lower slot on a tie) as
+// G_Y = W G W^T; the Weiszfeld loop of launch_gram_fixed_point from the
+// uniform start over the live rows (f64, not rounded to f32), stopped per
+// node; the pull-back W^T a scattered into row i of A (M, n) f32, which is
+// written completely. steps (M,) int32. Dead rows as above; a mixed row is
+// dead where its own row is. 1 <= n <= GRAMFP_MAX_N, 1 <= M <= GRAMFP_MAX_N,
+// 1 <= m <= GOSSIP_MAX_M. f64, fixed order, no atomics, no host sync.
+constexpr int GOSSIP_MAX_M = 32;
+void launch_gossip_solve(const float* G, const int* groups, int n, int M, int m,
+                         int nnm_f, double eps, double tol2, int iters,
+                         float* A, int* steps, hipStream_t stream);
+// combine_batched.hip (K23): out (M, d) = A (M, n) X (n, d) in T, f32
+// accumulation on the matrix pipe (bf16: A split exactly into three bf16
+// parts). One pass: a read row of X comes from HBM once, rows under an
+// all-zero column of A are never read, every output element is written once.
+// Bitwise repeatable, no atomics. A non-finite entry of a read row may make
+// its column of every output non-finite. 1 <= n, M <= GRAMFP_MAX_N, d >= 1,
+// any alignment.
+template <typename T>
+void launch_combine_batched(const T* X, const float* A, T* out, int n, int M,
+                            long d, hipStream_t stream);
 // rowptrs.hip (K20): out = sum_i coef[i] x_i, not normalised, f32 accumulation
 // in row order, out in T. Rows with coef[i] == 0 are never read. X null: the
 // rows are the table's (n <= ROWPTR_MAX_N); else rows of the contiguous (n, d)

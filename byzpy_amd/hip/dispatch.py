@@ -943,6 +943,108 @@ def mixed_geometric_median(
     )
 
 
+# -- a gossip round on one shared Gram (K23) ----------------------------------
+#
+# All node states are rows of one (N, d) matrix, so ONE Gram of it holds every
+# node's neighbourhood sub-Gram. A round for all nodes is that Gram (one pass),
+# weiszfeld_iter(G, groups=...) (one launch, N m^2 numbers) and
+# mean_rows(theta, coeffs=A) with the (M, N) coefficient matrix (one pass):
+# no (M, m, d) gather, no mixed matrix, no pass per Weiszfeld step.
+
+# Neighbourhood cap of weiszfeld_iter(G, groups=) (GOSSIP_MAX_M in
+# csrc/launchers.h); its node count and mean_rows(X, coeffs=A)'s M share
+# GRAMFP_MAX_N.
+GOSSIP_MAX_M = 32
+
+
+def gossip_groups(rows, device=None) -> torch.Tensor:
+    """The int32 (M, m) groups tensor of a list of per-node row lists, ragged
+    ones padded with -1. Checked on the host, before any device copy: the
+    entries of a list must be distinct and >= 0."""
+    rows = [[int(j) for j in r] for r in rows]
+    m = max((len(r) for r in rows), default=0)
+    if m < 1:
+        raise ValueError("every node needs at least one row")
+    for r in rows:
+        if not r or len(set(r)) != len(r) or min(r) < 0:
+            raise ValueError("a node's rows must be distinct, >= 0 and not empty")
+    padded = [r + [-1] * (m - len(r)) for r in rows]
+    return torch.tensor(padded, dtype=torch.int32, device=device)
+
+
+def _gossip_fused(G: torch.Tensor, groups: torch.Tensor) -> bool:
+    return (
+        _gpu(G)
+        and G.dtype == torch.float32
+        and 1 <= G.shape[0] <= GRAMFP_MAX_N
+        and 1 <= groups.shape[0] <= GRAMFP_MAX_N
+        and 1 <= groups.shape[1] <= GOSSIP_MAX_M
+    )
+
+
+def gossip_coeffs(
+    G: torch.Tensor,
+    groups: torch.Tensor,
+    nnm_f: Optional[int] = None,
+    *,
+    iters: int,
+    eps: float = 1e-12,
+    tol: float = 0.0,
+):
+    """(A, steps) of F.gossip_coeffs: one launch and no host sync for an f32
+    device Gram of n <= GRAMFP_MAX_N rows, M <= GRAMFP_MAX_N nodes and
+    neighbourhoods of m <= GOSSIP_MAX_M rows (A is f32, steps a device
+    tensor), the f64 loop otherwise."""
+    if nnm_f is not None and not 0 <= int(nnm_f) < groups.shape[1]:
+        raise ValueError("need 0 <= nnm_f < m")
+    if _gossip_fused(G, groups):
+        grp = groups.to(device=G.device, dtype=torch.int32).contiguous()
+        return tuple(_hip.require().weiszfeld_iter(
+            G.contiguous(), groups=grp, nnm_f=-1 if nnm_f is None else int(nnm_f),
+            eps=float(eps), tol=float(tol), iters=int(iters),
+        ))
+    return F.gossip_coeffs(G, groups, nnm_f, iters=iters, eps=eps, tol=tol)
+
+
+def combine_rows_batched(X: torch.Tensor, A: torch.Tensor) -> torch.Tensor:
+    """A @ X in X's dtype for an (M, n) coefficient matrix: one pass over the
+    rows of X that some row of A reads, f32 accumulation on the matrix pipe
+    (combine_batched.hip), for n, M <= GRAMFP_MAX_N on the device; the f64
+    product over the read rows elsewhere."""
+    if _gramfp_fused(X) and not _row_list(X) and 1 <= A.shape[0] <= GRAMFP_MAX_N:
+        A32 = A.to(device=X.device, dtype=torch.float32).contiguous()
+        return _hip.require().mean_rows(X.contiguous(), coeffs=A32)
+    A = A.to(X.device)
+    keep = (A != 0).any(dim=0)
+    return (A[:, keep].double() @ X[keep].double()).to(X.dtype)
+
+
+def gossip_geometric_median(
+    theta: torch.Tensor,
+    groups: torch.Tensor,
+    *,
+    nnm_f: Optional[int] = None,
+    fixed_iters: Optional[int] = None,
+    tol: float = 1e-6,
+    max_iter: int = 256,
+    eps: float = 1e-12,
+    centered: bool = False,
+) -> torch.Tensor:
+    """One gossip round of GeometricMedian(solver="gram", init="mean"), after
+    NNM(nnm_f) if given, for every node at once: row i of the (M, d) result is
+    the rule over the rows theta[groups[i]] (-1 pads). Gram, solver and combine
+    are three device steps with no host sync (capture-safe with
+    ``fixed_iters``); CPU tensors and shapes past the kernels' caps take the
+    f64 route. ``centered`` solves on the centred Gram of theta: valid, the
+    coefficients sum to 1 from the first step. Rows of theta that hold inf or
+    NaN get coefficient 0 everywhere and are not read by the combine."""
+    iters = int(fixed_iters) if fixed_iters is not None else int(max_iter)
+    tol = 0.0 if fixed_iters is not None else float(tol)
+    G = solver_gram(theta, centered)
+    A, _ = gossip_coeffs(G, groups, nnm_f, iters=iters, eps=eps, tol=tol)
+    return combine_rows_batched(theta, A)
+
+
 def _centered_clipping_gram(X, *, c_tau, M, eps, init) -> torch.Tensor:
     if init not in ("mean", "zero"):
         raise ValueError(

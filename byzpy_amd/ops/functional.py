@@ -428,6 +428,66 @@ def gram_fixed_point(
     return a, steps, shift2
 
 
+def gossip_coeffs(
+    G: torch.Tensor,
+    groups: torch.Tensor,
+    nnm_f: Optional[int] = None,
+    *,
+    iters: int,
+    eps: float = 1e-12,
+    tol: float = 0.0,
+):
+    """A gossip round in coefficient space on the Gram G (n, n) of ALL
+    resident rows, in f64. Row i of ``groups`` (M, m) lists the rows node i
+    aggregates (-1 pads; the valid entries are distinct). Per node: the
+    sub-Gram of its rows; with ``nnm_f`` nearest-neighbour mixing on it (row r
+    keeps its k = max(live - nnm_f, 1) nearest live rows by
+    G_rr + G_ss - 2 G_rs, itself included, the lower slot on a tie) as
+    G_Y = W G W^T; ``gram_fixed_point``'s Weiszfeld loop from the uniform
+    start over the live rows; the pull-back W^T a. A slot is dead where it is
+    padded or its G_ii is not finite, and a mixed row is dead where its own
+    row is. Returns (A f64 (M, n), steps int64 (M,)): the round is A @ X.
+
+    The oracle of the one-launch device solver (hip/csrc/gramfp.hip) and the
+    route of the gossip round wherever that kernel does not apply."""
+    Gd = G.double()
+    n = Gd.shape[0]
+    rows = groups.to(device=Gd.device, dtype=torch.long)
+    M = rows.shape[0]
+    A = torch.zeros((M, n), dtype=torch.float64, device=Gd.device)
+    steps = torch.zeros(M, dtype=torch.long, device=Gd.device)
+    inf = float("inf")
+    for i in range(M):
+        idx = rows[i][(rows[i] >= 0) & (rows[i] < n)]
+        m = int(idx.numel())
+        if m == 0:
+            continue
+        S = Gd[idx][:, idx]
+        live = torch.isfinite(torch.diagonal(S))
+        pair = live[:, None] & live[None, :] & torch.isfinite(S)
+        S = torch.where(pair, S, torch.zeros_like(S))
+        nlive = int(live.sum())
+        W = None
+        if nnm_f is not None:
+            k = max(nlive - int(nnm_f), 1)
+            diag = torch.diagonal(S)
+            D2 = diag[:, None] + diag[None, :] - 2.0 * S
+            D2 = torch.where(live[None, :], D2, torch.full_like(D2, inf))
+            # a stable sort ranks equal distances by slot
+            order = torch.sort(D2, dim=1, stable=True).indices[:, :k]
+            W = torch.zeros_like(S).scatter_(1, order, 1.0 / k)
+            W = torch.where(live[:, None] & live[None, :], W, torch.zeros_like(W))
+            S = W @ S @ W.T
+        S = S + torch.diag(torch.where(live, 0.0, inf).to(S.dtype))
+        a0 = live.double() / max(nlive, 1)
+        a, st, _ = gram_fixed_point(
+            S, a0, rule="weiszfeld", iters=iters, eps=eps, tol=tol
+        )
+        A[i, idx] = a if W is None else W.T @ a
+        steps[i] = st
+    return A, steps
+
+
 def mda_subset(D2: torch.Tensor, f: int) -> Tuple[int, ...]:
     """Exact minimum-diameter (n-f)-subset search on a squared-distance
     matrix. Branch-and-bound DFS with prefix-max pruning — runs on the host
