@@ -19,7 +19,7 @@ CSRC = PKG_DIR / "hip" / "csrc"
 OUT_SO = PKG_DIR / "_hip_ops.so"
 BUILD_DIR = PKG_DIR.parent / "build" / "hip"
 
-SOURCES = ["colsel.hip", "colsel_mix.hip", "rsel.hip", "rowops.hip", "gram.hip",
+SOURCES = ["colsel.hip", "colsel_mix.hip", "colsel_groups.hip", "rsel.hip", "rowops.hip", "gram.hip",
            "gram_centered.hip", "rowptrs.hip", "krumsel.hip", "subsets.hip", "gramfp.hip", "combine_batched.hip",
            "attacks.hip",
            "mda_host.cpp", "bind.cpp"]
@@ -39,6 +39,7 @@ EXTRA_FLAGS = {
     "gramfp.hip": _NO_PK_F32,
     "gram_centered.hip": _NO_PK_F32,
     "combine_batched.hip": _NO_PK_F32,
+    "colsel_groups.hip": _NO_PK_F32,
 }
 
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")

@@ -296,6 +296,38 @@ torch::Tensor colsel_mix(torch::Tensor X, int64_t mode, int64_t f,
   return out;
 }
 
+// colsel(X, mode, f, groups=G, min_m=k): the statistic for M row sets of X in
+// one pass (colsel_groups.hip, K24). G is int32 (M, m) on X's device, -1 pads
+// at the end of a row; row i of the (M, d) result is what colsel(X, mode, f,
+// rows=G[i] valid) returns. min_m is the smallest valid count of a row of G:
+// the counts live on the device, and the host caller that built the table
+// knows them, so f is checked against it here with no host sync.
+torch::Tensor colsel_groups(torch::Tensor X, int64_t mode, int64_t f,
+                            torch::Tensor groups, int64_t min_m) {
+  check_matrix(X);
+  check_i32(groups, 2, "groups");
+  TORCH_CHECK(groups.device() == X.device(), "groups: expected X's device");
+  const int64_t n = X.size(0), M = groups.size(0), m = groups.size(1);
+  const long d = (long)X.size(1);
+  TORCH_CHECK(n >= 1 && n <= GRAMFP_MAX_N, "colsel(groups=) supports 1 <= n <= ",
+              GRAMFP_MAX_N, ", got ", n);
+  TORCH_CHECK(M >= 1 && M <= GRAMFP_MAX_N && m >= 1 && m <= GOSSIP_MAX_M,
+              "groups: expected (M, m) with 1 <= M <= ", GRAMFP_MAX_N,
+              " and 1 <= m <= ", GOSSIP_MAX_M, ", got (", M, ", ", m, ")");
+  TORCH_CHECK(mode >= 0 && mode <= 2, "colsel(groups=): expected mode 0, 1 or 2");
+  TORCH_CHECK(min_m >= 1 && min_m <= m, "min_m: expected 1 <= min_m <= ", m,
+              ", got ", min_m);
+  check_colsel_f(mode, f, min_m);
+  auto out = torch::empty({M, (int64_t)d}, X.options());
+  if (d == 0) return out;
+  by_dtype(X, [&](auto tag) {
+    using T = TAG_T(tag);
+    launch_colsel_groups<T>(ptr<T>(X), i32(groups), ptr<T>(out), (int)n, (int)M,
+                            (int)m, d, (int)mode, (int)f, cur_stream());
+  });
+  return out;
+}
+
 torch::Tensor row_sqnorms(torch::Tensor X) {
   check_matrix(X);
   const int n = (int)X.size(0);
@@ -1161,6 +1193,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "median / trimmed mean of the rows mixed by a membership matrix (K18)",
         py::arg("X"), py::arg("mode"), py::arg("f"), py::kw_only(),
         py::arg("mix"));
+  m.def("colsel", &colsel_groups,
+        "the same statistics for M row sets of X in one pass (K24): (M, d)",
+        py::arg("X"), py::arg("mode"), py::arg("f"), py::kw_only(),
+        py::arg("groups"), py::arg("min_m"));
   m.def("colsel", &colsel_rowlist,
         "the same statistics over a list of n <= 64 1-D device rows (K19)",
         py::arg("rows"), py::arg("mode"), py::arg("f"));

@@ -181,6 +181,18 @@ void launch_gossip_solve(const float* G, const int* groups, int n, int M, int m,
 template <typename T>
 void launch_combine_batched(const T* X, const float* A, T* out, int n, int M,
                             long d, hipStream_t stream);
+// colsel_groups.hip (K24): launch_colsel's three modes for M row sets of the
+// (n, d) matrix X in one pass over it. groups (M, m) int32 lists per node the
+// rows it aggregates, -1 pads at the end of a row; indices are clamped to
+// [0, n). Row i of out (M, d) is the statistic over node i's m_i valid rows
+// with parameter f, which must be legal for every m_i (the caller checks; an
+// empty or too short node gives an unspecified in-bounds result). Median and
+// trimmed mean agree bit for bit with launch_colsel(rows=) over the same rows.
+// 1 <= n, M <= GRAMFP_MAX_N, 1 <= m <= GOSSIP_MAX_M, d >= 1, any alignment.
+// One launch, no scratch, no atomics, no host sync.
+template <typename T>
+void launch_colsel_groups(const T* X, const int* groups, T* out, int n, int M,
+                          int m, long d, int mode, int f, hipStream_t stream);
 // rowptrs.hip (K20): out = sum_i coef[i] x_i, not normalised, f32 accumulation
 // in row order, out in T. Rows with coef[i] == 0 are never read. X null: the
 // rows are the table's (n <= ROWPTR_MAX_N); else rows of the contiguous (n, d)

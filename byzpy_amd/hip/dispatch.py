@@ -77,9 +77,60 @@ def _colsel_row_list(rows, mode: int, f: int) -> torch.Tensor:
     return _hip.require().colsel(list(rows), mode, int(f))
 
 
-def median(X: torch.Tensor, rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+def _group_counts(groups: torch.Tensor):
+    """Valid entries per row of a groups table. gossip_groups leaves them on
+    the tensor it builds; any other device table is copied to the host."""
+    counts = getattr(groups, "valid_counts", None)
+    if counts is None:
+        counts = (groups >= 0).sum(dim=1).tolist()
+    return counts
+
+
+def _colsel_groups(X, mode: int, f: int, groups, rows, per_node):
+    """``groups=`` of median / trimmed_mean / mean_of_medians (K24): the
+    statistic for every row set of an (M, m) table (gossip_groups, or a list
+    of row lists) at once, (M, d). A device f32 / bf16 matrix of N <=
+    COLSEL_GROUPS_MAX_N rows with M <= COLSEL_GROUPS_MAX_N and m <=
+    COLSEL_GROUPS_MAX_M is one pass over X (colsel_groups.hip); anything else
+    is ``per_node`` on X[g] per node, stacked."""
+    if rows is not None or _row_list(X):
+        raise ValueError("groups= goes with one (N, d) matrix and without rows=")
+    if not isinstance(groups, torch.Tensor):
+        groups = gossip_groups(groups, X.device)
+    if groups.dim() != 2 or groups.shape[0] < 1 or groups.shape[1] < 1:
+        raise ValueError("groups must be a non-empty (M, m) table")
+    counts = _group_counts(groups)
+    f = int(f)
+    need = f + 1 if mode == _COLSEL_MEAMED else 2 * f + 1
+    if f < 0 or min(counts) < need:
+        raise ValueError(
+            f"f={f} needs at least {need} rows per node, the smallest has {min(counts)}"
+        )
+    M, m = groups.shape
+    if (
+        _gpu(X)
+        and X.dtype in (torch.float32, torch.bfloat16)
+        and X.shape[0] <= COLSEL_GROUPS_MAX_N
+        and M <= COLSEL_GROUPS_MAX_N
+        and m <= COLSEL_GROUPS_MAX_M
+    ):
+        grp = groups.to(device=X.device, dtype=torch.int32).contiguous()
+        return _hip.require().colsel(
+            X.contiguous(), mode, f, groups=grp, min_m=int(min(counts))
+        )
+    lists = [[j for j in g if j >= 0] for g in groups.tolist()]
+    return torch.stack([per_node(X[g]) for g in lists])
+
+
+def median(
+    X: torch.Tensor, rows: Optional[torch.Tensor] = None, groups=None
+) -> torch.Tensor:
     """``rows`` (m distinct row indices) restricts the statistic to those
-    rows, as if on X[rows]; same for trimmed_mean and mean_of_medians."""
+    rows, as if on X[rows]; ``groups`` (an (M, m) table of row sets, -1 pads)
+    gives the (M, d) statistics of all its sets; same for trimmed_mean and
+    mean_of_medians."""
+    if groups is not None:
+        return _colsel_groups(X, _COLSEL_MEDIAN, 0, groups, rows, median)
     if _row_list(X):
         return _colsel_row_list(X, _COLSEL_MEDIAN, 0)
     if rows is not None:
@@ -91,8 +142,12 @@ def median(X: torch.Tensor, rows: Optional[torch.Tensor] = None) -> torch.Tensor
 
 
 def trimmed_mean(
-    X: torch.Tensor, f: int, rows: Optional[torch.Tensor] = None
+    X: torch.Tensor, f: int, rows: Optional[torch.Tensor] = None, groups=None
 ) -> torch.Tensor:
+    if groups is not None:
+        return _colsel_groups(
+            X, _COLSEL_TRIMMED, f, groups, rows, lambda Y: trimmed_mean(Y, f)
+        )
     if _row_list(X):
         return _colsel_row_list(X, _COLSEL_TRIMMED, f)
     if rows is not None:
@@ -104,8 +159,12 @@ def trimmed_mean(
 
 
 def mean_of_medians(
-    X: torch.Tensor, f: int, rows: Optional[torch.Tensor] = None
+    X: torch.Tensor, f: int, rows: Optional[torch.Tensor] = None, groups=None
 ) -> torch.Tensor:
+    if groups is not None:
+        return _colsel_groups(
+            X, _COLSEL_MEAMED, f, groups, rows, lambda Y: mean_of_medians(Y, f)
+        )
     if _row_list(X):
         return _colsel_row_list(X, _COLSEL_MEAMED, f)
     if rows is not None:
@@ -955,12 +1014,18 @@ def mixed_geometric_median(
 # csrc/launchers.h); its node count and mean_rows(X, coeffs=A)'s M share
 # GRAMFP_MAX_N.
 GOSSIP_MAX_M = 32
+# Caps of colsel(X, mode, f, groups=) (csrc/colsel_groups.hip, K24): rows of X
+# and nodes, and rows per node. The K23 caps, so one table serves both.
+COLSEL_GROUPS_MAX_N = GRAMFP_MAX_N
+COLSEL_GROUPS_MAX_M = GOSSIP_MAX_M
 
 
 def gossip_groups(rows, device=None) -> torch.Tensor:
     """The int32 (M, m) groups tensor of a list of per-node row lists, ragged
     ones padded with -1. Checked on the host, before any device copy: the
-    entries of a list must be distinct and >= 0."""
+    entries of a list must be distinct and >= 0. The tensor carries the list
+    lengths as ``valid_counts``, for callers that need them without reading
+    the device copy back."""
     rows = [[int(j) for j in r] for r in rows]
     m = max((len(r) for r in rows), default=0)
     if m < 1:
@@ -969,7 +1034,9 @@ def gossip_groups(rows, device=None) -> torch.Tensor:
         if not r or len(set(r)) != len(r) or min(r) < 0:
             raise ValueError("a node's rows must be distinct, >= 0 and not empty")
     padded = [r + [-1] * (m - len(r)) for r in rows]
-    return torch.tensor(padded, dtype=torch.int32, device=device)
+    groups = torch.tensor(padded, dtype=torch.int32, device=device)
+    groups.valid_counts = [len(r) for r in rows]
+    return groups
 
 
 def _gossip_fused(G: torch.Tensor, groups: torch.Tensor) -> bool:
